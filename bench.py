@@ -26,8 +26,15 @@ with the pack fused into the env-step kernel and one all-gather + consume per ba
 library's own RCCL communicator (PipelinedObsGather.run / cf2_xchg_run); `value` = 262 144 x K
 env-steps / the max over ranks of the timed region.  Extra keys: "collective_free" (the same split
 without the gather: the fallback headline, with "gather_obs": false and the error stated, if the
-gather fails) and "weak_scaling" (every rank stepping 262 144 envs of its own).  --scaling weak
+gather fails) and, with --full, "weak_scaling" (every rank stepping 262 144 envs of its own).  --scaling weak
 makes the weak run the headline instead (the gather then an extra key).
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K env-steps and prints
+the line; the keys measured beside the headline ("cpu_baseline", "fused_rollout", "collect",
+"streaming_actions", "two_streams", "delta_exchange", the roofline's "out_of_cache" with the HBM
+probe, a non-headline "gather", "weak_scaling" / "strong_scaling") are null unless --full is given.
+--dump-outputs DIR writes what the last timed env-step returned (obs, rew, done, trunc, cost, level)
+as DIR/<name>.npy; the same arguments give the same inputs, so two builds can be compared.
 """
 from __future__ import annotations
 
@@ -302,7 +309,44 @@ def parse_args(argv=None):
                          "(all 262 144 rows) kernels on this GPU; 0 = skip")
     ap.add_argument("--rollout-k", type=int, default=32,
                     help="also time the fused K-step rollout (cf2_rollout, random actions) on 1 GPU; 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the CPU baseline, the fused rollout, the collect "
+                         "loop, the streaming-action, out-of-cache and HBM-probe lines, the node-shard exchange probe, "
+                         "--two-streams, the gather as an extra key and, at N > 1, the weak / strong scaling keys "
+                         "(each still sized or skipped by its own option).  Without it a run sets up, warms up, times "
+                         "--steps env-steps and prints the line with those keys null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed env-steps, write what the last of them returned (obs, rew, done, trunc, cost, "
+                         "level of this rank's envs) as DIR/<name>.npy in float32 (DIR/<name>.rank<r>.npy at N > 1); "
+                         f"beyond {DUMP_MAX_BYTES >> 20} MB in all, a fixed seeded sample of the env rows")
     return ap.parse_args(argv)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(env, out_dir: str, rank: int, world: int) -> None:
+    """Write the outputs of the env-step launched last (the arrays step() hands its caller) to
+    out_dir as float32 .npy files.  All of them together stay below DUMP_MAX_BYTES over the whole
+    job: a larger batch is cut to a sorted sample of env rows drawn with a fixed seed, the same rows
+    in every array and in every run."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    arrays = {name: getattr(env, name) for name in BOUNDARY_OUTPUTS}
+    n = env.num_envs
+    row_bytes = sum(4 * (a.numel() // n) for a in arrays.values())
+    keep = (DUMP_MAX_BYTES // world - 1024 * len(arrays)) // row_bytes          # 1 KB per file for its header
+    rows = None
+    if keep < n:
+        rows = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False)))
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}.npy" if world > 1 else ".npy"
+    for name, a in arrays.items():
+        h = a.cpu()
+        if rows is not None:
+            h = h[rows]
+        np.save(os.path.join(out_dir, name + suffix), h.to(torch.float32).numpy())
 
 
 def bind_synthetic_tables(env, dev):
@@ -468,6 +512,9 @@ def main(argv=None):
     if args.gpus is not None and args.gpus != world:
         raise SystemExit(f"bench.py: --gpus {args.gpus}, but the launcher started {world} ranks")
     env_kw = json.loads(args.env_kw)
+    full = bool(args.full)
+    if not full and args.two_streams:
+        raise SystemExit("bench.py: the two_streams key is measured beside the headline; pass --full with --two-streams")
 
     import torch
     import torch.distributed as dist
@@ -515,6 +562,11 @@ def main(argv=None):
     headline_gather = gather and world > 1 and scaling == "strong"
     if headline_gather and args.gather_envs != global_envs:
         raise SystemExit("bench.py: the gathered headline splits --global-envs; pass the same --gather-envs")
+    if gather and not headline_gather and not full:
+        # the gather as an extra key beside the headline: on request only
+        if args.gather_obs:
+            raise SystemExit("bench.py: here the gather is a key beside the headline; pass --full with --gather-obs")
+        gather = False
 
     def max_over_ranks(x: float) -> float:
         if not use_pg:
@@ -580,9 +632,11 @@ def main(argv=None):
     # ---- timed region: exactly K steps between barrier + synchronize, max over ranks ----
     elapsed, ev_ms = run(args.steps, graph)
     kern_ms = ev_ms / args.steps
+    if args.dump_outputs:
+        dump_outputs(env, args.dump_outputs, rank, world)
 
     weak = None
-    if world > 1 and scaling == "strong" and args.weak_steps > 0:
+    if full and world > 1 and scaling == "strong" and args.weak_steps > 0:
         # every rank stepping 262 144 envs of its own global ids, no collective (weak scaling)
         wn = METRIC_GLOBAL_ENVS
         wenv = BatchedCrazyflieEnv(args.env_id, wn, seed=args.seed, env_id_offset=rank * wn, device=dev, **env_kw)
@@ -606,7 +660,7 @@ def main(argv=None):
         del wacts
 
     strong = None
-    if world > 1 and scaling == "weak" and args.strong_steps > 0:
+    if full and world > 1 and scaling == "weak" and args.strong_steps > 0:
         # the same 262 144 envs split over the ranks (32 768 per GPU at N = 8), no collective
         so, sn = shard_range(METRIC_GLOBAL_ENVS, rank, world)
         senv = BatchedCrazyflieEnv(args.env_id, sn, seed=args.seed, env_id_offset=so, device=dev, **env_kw)
@@ -630,7 +684,7 @@ def main(argv=None):
         del sacts
 
     fused = None
-    if world == 1 and args.rollout_k > 0:
+    if full and world == 1 and args.rollout_k > 0:
         # the north star's "synthetic random-action rollouts" with the actions known in advance:
         # K env-steps per launch, the state in registers; every step's outputs written to its slab
         K = args.rollout_k
@@ -658,7 +712,7 @@ def main(argv=None):
         del racts
 
     collect_line = None
-    if world == 1 and args.collect_steps > 0:
+    if full and world == 1 and args.collect_steps > 0:
         # the f3 caller: PPO/IWPG data collection (algs/iwpg/iwpg.py:372-410) over the batch with the
         # reference's default actor-critic (random init), one cf2_collect_step launch per env-step
         # (env-step + policy forward on its observations), GAE and the time-out values after the loop
@@ -714,7 +768,7 @@ def main(argv=None):
         cenv.close()
 
     two_streams = None
-    if world == 1 and args.two_streams and n % 128 == 0:
+    if full and world == 1 and args.two_streams and n % 128 == 0:
         # the same envs as two contexts of n / 2 consecutive global ids, each stepping on its own HIP
         # stream with no per-step join: shard A's env-step k + 1 overlaps shard B's env-step k (the
         # launch ramp and tail of one hide under the other).  Same trajectories (split invariance).
@@ -756,7 +810,7 @@ def main(argv=None):
         del halves
 
     streaming = None
-    if world == 1 and args.streaming_ring > 0:
+    if full and world == 1 and args.streaming_ring > 0:
         # the same env-step with the actions cycled through a ring larger than the Infinity Cache
         # (as a training loop's fresh action / rollout buffers do): the env state (~165 MB at 262 144
         # envs) then no longer stays cache-resident between steps, so this is the HBM-streaming rate
@@ -779,7 +833,7 @@ def main(argv=None):
 
     from cf2sim.dist import delta_supported
     exchange = None
-    if world == 1 and args.exchange_probe and n == METRIC_GLOBAL_ENVS and delta_supported(env.cfg):
+    if full and world == 1 and args.exchange_probe and n == METRIC_GLOBAL_ENVS and delta_supported(env.cfg):
         # the delta obs exchange of the 8-GPU shape on one GPU: 8 shards of this step's real rows
         # and done flags packed as the ranks would (cf2_obs_pack, 32 768 rows each), then a rank's
         # per-step consume of all 262 144 envs (cf2_obs_consume: the ages) and, on request, the
@@ -875,7 +929,7 @@ def main(argv=None):
 
     bytes_per = bytes_per_env_step(env)
     out_of_cache = None
-    if world == 1 and args.oc_envs > 0:
+    if full and world == 1 and args.oc_envs > 0:
         # out of the Infinity Cache: at 1 Mi envs the env state alone is ~500 MB, so every env-step
         # reads and writes it in HBM (the PMC byte counters, which include Infinity-Cache hits, then
         # measure HBM traffic: profiles/, tools/pmc_traffic.sh)
@@ -936,7 +990,7 @@ def main(argv=None):
     line = None
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.cpu_envs, args.cpu_steps)
         line = {
             "metric": "env-steps/sec (whole node) at 262k parallel envs; achieved HBM GB/s vs peak",

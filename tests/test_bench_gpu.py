@@ -42,9 +42,81 @@ def _line(stdout):
     return json.loads(lines[0])
 
 
+EXTRA_KEYS = ("cpu_baseline", "gather", "collective_free", "strong_scaling", "weak_scaling", "fused_rollout", "collect",
+              "streaming_actions", "two_streams", "delta_exchange")
+
+
+def test_plain_run_times_the_steps_only_and_dumps_their_outputs(gpu, tmp_path):
+    """A plain run (no --full) measures the headline alone: every key beside it is null.
+    --dump-outputs writes what the last timed env-step returned: bit for bit what the same env,
+    seed and action ring give after warmup + steps env-steps in this process."""
+    import numpy as np
+    from cf2sim.vec_env import BatchedCrazyflieEnv
+    n, steps, warmup = 4096, 20, 5
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+                        str(warmup), "--global-envs", str(n), "--dump-outputs", str(out)], env=_env(),
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = _line(p.stdout)
+    assert d["steps"] == steps and d["warmup"] == warmup and d["config"]["envs_per_gpu"] == n
+    assert d["value"] > 0 and d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - n / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["roofline"]["kernel_ms_per_launch"] > 0 and d["roofline"]["out_of_cache"] is None
+    assert all(d[k] is None for k in EXTRA_KEYS), {k: d[k] for k in EXTRA_KEYS if d[k] is not None}
+    env = BatchedCrazyflieEnv("DroneHoverBulletFreeEnvWithGust-v0", n, seed=0, device="cuda:0")
+    env.reset()
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(1234)
+    acts = torch.rand(8, n, 4, device="cuda:0", generator=g) * 2 - 1
+    for count in (warmup, steps):
+        for k in range(count):
+            env.step_raw(acts[k % 8].data_ptr())
+    torch.cuda.synchronize()
+    assert sorted(os.listdir(out)) == sorted(f"{name}.npy" for name in ("obs", "rew", "done", "trunc", "cost", "level"))
+    for name in ("obs", "rew", "done", "trunc", "cost", "level"):
+        a = np.load(out / f"{name}.npy")
+        want = getattr(env, name).cpu().to(torch.float32).numpy()
+        assert a.dtype == np.float32 and a.shape == want.shape, (name, a.dtype, a.shape)
+        assert np.array_equal(a, want), name
+    assert np.isfinite(np.load(out / "obs.npy")).all() and np.abs(np.load(out / "obs.npy")).max() > 0
+    env.check_device_errors()
+    env.close()
+
+
+def test_dump_outputs_samples_the_same_rows_beyond_the_size_limit(gpu, tmp_path, monkeypatch):
+    """Beyond the size limit the dump is a sample of env rows: the same rows in every array and in
+    every call, the files together below the limit."""
+    import numpy as np
+    import bench
+    from cf2sim.vec_env import BatchedCrazyflieEnv
+    n = 1000
+    env = BatchedCrazyflieEnv("DroneHoverBulletFreeEnvWithGust-v0", n, seed=2, device="cuda:0")
+    env.reset()
+    env.step(torch.zeros(n, 4, device="cuda:0"))
+    env.rew.copy_(torch.arange(n, device="cuda:0"))            # marks each row with its index
+    env.cost.copy_(torch.arange(n, device="cuda:0"))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 64 << 10)
+    bench.dump_outputs(env, str(tmp_path / "a"), 0, 1)
+    bench.dump_outputs(env, str(tmp_path / "b"), 0, 1)
+    a = {name: np.load(tmp_path / "a" / f"{name}.npy") for name in bench.BOUNDARY_OUTPUTS}
+    rows = a["rew"].astype(np.int64)
+    assert 300 < len(rows) < n and (np.diff(rows) > 0).all() and np.array_equal(a["cost"], a["rew"])
+    assert np.array_equal(a["obs"], env.obs.cpu().numpy()[rows]) and a["obs"].dtype == np.float32
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 << 10
+    for name in bench.BOUNDARY_OUTPUTS:
+        assert np.array_equal(a[name], np.load(tmp_path / "b" / f"{name}.npy")), name
+    # within the limit: every row
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 64 << 20)
+    bench.dump_outputs(env, str(tmp_path / "c"), 0, 1)
+    assert np.array_equal(np.load(tmp_path / "c" / "obs.npy"), env.obs.cpu().numpy())
+    env.close()
+
+
 def test_bench_self_launches_two_ranks(gpu):
     env = dict(_env(), CF2_BENCH_BACKEND="gloo")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *SHORT], env=env,
+    # --full: the weak-scaling key is measured beside the headline
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", *SHORT], env=env,
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _line(p.stdout)
@@ -94,8 +166,8 @@ def test_bench_two_ranks_native_exchange_headline(gpu):
 
 def test_bench_rccl_gather_path_one_rank(gpu):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-           "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--gather-obs",
-           "--gather-envs", "32768", *SHORT]
+           "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full",
+           "--gather-obs", "--gather-envs", "32768", *SHORT]      # --full: at N = 1 the gather is an extra key
     p = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _line(p.stdout)
@@ -152,7 +224,7 @@ def test_bench_hj_config_runs_the_node_shard_probe(gpu):
     # every BASELINE config goes through the same line (tools/all_configs.sh): on the HJ-adversary
     # env the node-shard exchange probe's own env must have value tables bound too
     assert SHORT[-2:] == ["--exchange-probe", "0"]
-    args = SHORT[:-2] + ["--exchange-probe", "1"]
+    args = SHORT[:-2] + ["--exchange-probe", "1", "--full"]
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--env-id",
                         "DroneHoverBulletFreeEnvWithAdversary-v0", *args], env=_env(), capture_output=True,
                        text=True, timeout=600, cwd=ROOT)

@@ -89,6 +89,18 @@ def test_bench_defaults_are_the_metric_config():
     assert bench.parse_args(["--no-gather-obs"]).gather_obs is False
 
 
+def test_a_plain_run_is_the_default_and_extras_need_full(monkeypatch):
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    a = bench.parse_args(["--full", "--dump-outputs", "some/dir"])
+    assert a.full is True and a.dump_outputs == "some/dir"
+    # a key that is only ever measured beside the headline, asked for without --full: refused
+    # before anything touches the GPU, never silently dropped
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    with pytest.raises(SystemExit, match="--full"):
+        bench.main(["--two-streams", "1"])
+
+
 def test_gpus_mismatch_with_launcher_aborts(monkeypatch):
     monkeypatch.setenv("WORLD_SIZE", "2")
     with pytest.raises(SystemExit, match="launcher started 2 ranks"):
