@@ -105,6 +105,27 @@ def test_build_rejects_unknown_defines():
         build_native(extra_flags=["-DCF2_TIMING"])
 
 
+def test_every_header_is_in_the_content_key(tmp_path, monkeypatch):
+    """A change to any header of csrc/ changes the kernel object's content key (a header outside
+    the key would let a stale library be reused silently)."""
+    import glob
+    import shutil
+    from cf2sim import build
+    src = shutil.copytree(build.SRC_DIR, tmp_path / "csrc")
+    inc = shutil.copytree(build.INC_DIR, tmp_path / "include")
+    monkeypatch.setattr(build, "SRC_DIR", str(src))
+    monkeypatch.setattr(build, "INC_DIR", str(inc))
+    headers = sorted(glob.glob(os.path.join(str(src), "*.h")))
+    assert [os.path.basename(h) for h in headers] == list(build.HEADERS) and len(headers) > 4
+    key = build._obj_key("cf2sim_kernels.hip")
+    for h in headers + [os.path.join(str(inc), "cf2sim.h")]:
+        with open(h, "ab") as f:
+            f.write(b"\n")
+        new = build._obj_key("cf2sim_kernels.hip")
+        assert new != key, os.path.basename(h)
+        key = new
+
+
 def test_kernel_sources_hold_no_ab_branches():
     """The only preprocessor conditional in the native sources is CF2_TIMING."""
     import glob

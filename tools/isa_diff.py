@@ -1,0 +1,93 @@
+"""Per-kernel comparison of two device assembly listings of one source (hipcc --cuda-device-only -S
+with cf2sim.build._compile_flags(src)): which kernel instances are byte-identical (function text and
+.amdhsa_* descriptor), and the resources of those that are not.
+python tools/isa_diff.py BEFORE.s AFTER.s [--label TEXT]"""
+import argparse
+import re
+import shutil
+import subprocess
+
+RES = (("vgpr", "next_free_vgpr"), ("agpr_off", "accum_offset"), ("sgpr", "next_free_sgpr"),
+       ("lds", "group_segment_fixed_size"), ("scratch", "private_segment_fixed_size"))
+
+
+def kernels(path):
+    """{symbol: (function text, descriptor text, resources)} of every .amdhsa_kernel of the listing."""
+    lines = open(path).read().split("\n")
+    start = {}
+    for n, l in enumerate(lines):
+        m = re.match(r"^(\w+):\s*(;.*)?$", l)
+        if m:
+            start.setdefault(m.group(1), n)
+    out = {}
+    n = 0
+    while n < len(lines):
+        m = re.match(r"\s*\.amdhsa_kernel\s+(\w+)", lines[n])
+        if not m:
+            n += 1
+            continue
+        sym = m.group(1)
+        e = n
+        while ".end_amdhsa_kernel" not in lines[e]:
+            e += 1
+        desc = lines[n:e + 1]
+        b = start[sym]
+        f = b
+        while not lines[f].startswith(".Lfunc_end"):
+            f += 1
+        res = {}
+        for key, field in RES:
+            for d in desc:
+                mm = re.match(rf"\s*\.amdhsa_{field}\s+(\d+)", d)
+                if mm:
+                    res[key] = int(mm.group(1))
+        for l in lines[f:f + 60]:
+            mm = re.match(r";\s*Occupancy:\s*(\d+)", l)
+            if mm:
+                res["waves"] = int(mm.group(1))
+                break
+        # block labels carry the function's position in the listing, which moves with the order
+        # of instantiation: not a difference of the kernel
+        text = re.sub(r"\.LBB\d+_", ".LBB_", "\n".join(lines[b:f]))
+        out[sym] = (text, "\n".join(desc), res)
+        n = e + 1
+    return out
+
+
+def demangle(syms):
+    filt = shutil.which("llvm-cxxfilt") or shutil.which("c++filt")
+    if filt is None:
+        return {s: s for s in syms}
+    r = subprocess.run([filt], input="\n".join(syms), capture_output=True, text=True, check=True).stdout.split("\n")
+    return {s: re.sub(r"^(void )?cf2::", "", d) for s, d in zip(syms, r)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("before")
+    ap.add_argument("after")
+    ap.add_argument("--label", default="")
+    a = ap.parse_args()
+    A, B = kernels(a.before), kernels(a.after)
+    names = demangle(sorted(set(A) | set(B)))
+    same = [s for s in A if s in B and A[s][:2] == B[s][:2]]
+    diff = [s for s in A if s in B and A[s][:2] != B[s][:2]]
+    print(f"== {a.label}: {len(A)} -> {len(B)} kernel instances, {len(same)} identical, {len(diff)} changed, "
+          f"{len(set(A) - set(B))} removed, {len(set(B) - set(A))} added")
+    fam = {}
+    for s in same:
+        k = names[s].split("<")[0].split("(")[0]
+        fam[k] = fam.get(k, 0) + 1
+    for k in sorted(fam):
+        print(f"identical  {k} x{fam[k]}")
+    for s in diff:
+        ra, rb = A[s][2], B[s][2]
+        cols = " ".join(f"{k} {ra.get(k)}->{rb.get(k)}" if ra.get(k) != rb.get(k) else f"{k} {ra.get(k)}"
+                        for k in ("vgpr", "agpr_off", "sgpr", "lds", "scratch", "waves"))
+        print(f"changed    {names[s].split('(')[0]}: {cols}")
+    for s in sorted(set(A) ^ set(B)):
+        print(("removed    " if s in A else "added      ") + names[s].split("(")[0])
+
+
+if __name__ == "__main__":
+    main()

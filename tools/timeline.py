@@ -4,7 +4,7 @@ run with ``CF2SIM_LIB=build_ab/timing.so``).  Prints phase durations, how waves 
 SIMDs, and how many waves were resident per SIMD over time.
 
 Timing row per wave (16 x u64): 0 hw id (XCC << 32 | HW_ID), 1 realtime start, 2 realtime end,
-3 + k = s_memtime stamp k.  Stamps (cf2sim_kernels.hip, TSTAMP):
+3 + k = s_memtime stamp k.  Stamps (TSTAMP of cf2sim_timing.h, placed in cf2sim_step.h, cf2sim_reset.h and cf2sim_kernels.hip):
   step_kernel (N > 32 768, one lane per env, 4 env waves per block):
     0 entry, 1 state loads landed, 2 physics done, 3 epilogue issued, 4 block barrier passed,
     6 reset role start, 7 reset pose computed, 8 role-2 sensor call + history done,
