@@ -254,7 +254,7 @@ class BatchedCrazyflieEnv:
         Every buffer is checked (device, dtype, shape, contiguity, alignment): the kernel trusts them."""
         n, od, dev = self.num_envs, self.obs_dim, self.device
         _check_buf(actions, "actions", (n, 4), torch.float32, dev, 16)
-        _check_buf(obs_out, "obs_out", (n, od), torch.float32, dev, 16)
+        _check_buf(obs_out, "obs_out", (n, od), torch.float32, dev, 8)    # a slab of [K, N, D] storage, N odd
         _check_buf(rew_out, "rew_out", (n,), torch.float32, dev)
         _check_buf(done_out, "done_out", (n,), torch.uint8, dev, 1)
         _check_buf(trunc_out, "trunc_out", (n,), torch.uint8, dev, 1)
@@ -277,7 +277,7 @@ class BatchedCrazyflieEnv:
         no fused instance is built (cf2sim.h); the caller then makes the two calls."""
         n, od, dev = self.num_envs, self.obs_dim, self.device
         _check_buf(actions, "actions", (n, 4), torch.float32, dev, 16)
-        _check_buf(obs_out, "obs_out", (n, od), torch.float32, dev, 16)
+        _check_buf(obs_out, "obs_out", (n, od), torch.float32, dev, 8)    # a slab of [K, N, D] storage, N odd
         _check_buf(rew_out, "rew_out", (n,), torch.float32, dev)
         _check_buf(done_out, "done_out", (n,), torch.uint8, dev, 1)
         _check_buf(trunc_out, "trunc_out", (n,), torch.uint8, dev, 1)

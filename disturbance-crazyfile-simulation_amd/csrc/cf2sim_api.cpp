@@ -347,7 +347,9 @@ int cf2_step(cf2_ctx* ctx, const float* act_dev, const float* dstb_dev, float* o
     if (ctx->cfg.disturbance == CF2_DSTB_EXTERNAL && !dstb_dev) return CF2_ERR_INVALID_ARG;
     if (ctx->cfg.disturbance == CF2_DSTB_HJ && !ctx->P.V) return CF2_ERR_NO_TABLE;
     if (ctx->P.ground_effect) return CF2_ERR_UNSUPPORTED;       // physics plug-in only (cf2sim.h)
-    if (((uintptr_t)act_dev & 15u) != 0 || ((uintptr_t)obs_dev & 15u) != 0) return CF2_ERR_INVALID_ARG;
+    // obs rows go out as 16-B stores where obs_dev allows it and as 8-B stores otherwise (write_obs_rows):
+    // slab k of a contiguous [K, N, obs_dim] buffer is only 8-B aligned when N is odd
+    if (((uintptr_t)act_dev & 15u) != 0 || ((uintptr_t)obs_dev & 7u) != 0) return CF2_ERR_INVALID_ARG;
     if (final_obs_dev && ((uintptr_t)final_obs_dev & 7u) != 0) return CF2_ERR_INVALID_ARG;
     StepIO io{ctx->sf, act_dev, dstb_dev, obs_dev, rew_dev, done_dev, trunc_dev, cost_dev, level_dev,
               final_obs_dev};
@@ -383,7 +385,7 @@ int cf2_collect_step(cf2_ctx* ctx, const float* act_dev, float* obs_dev, float* 
     if (act_out_dev == act_dev) return CF2_ERR_INVALID_ARG;
     if (ctx->cfg.disturbance == CF2_DSTB_EXTERNAL || ctx->P.ground_effect) return CF2_ERR_UNSUPPORTED;
     if (ctx->cfg.disturbance == CF2_DSTB_HJ && !ctx->P.V) return CF2_ERR_NO_TABLE;
-    if (((uintptr_t)act_dev & 15u) != 0 || ((uintptr_t)obs_dev & 15u) != 0 || ((uintptr_t)act_out_dev & 15u) != 0 ||
+    if (((uintptr_t)act_dev & 15u) != 0 || ((uintptr_t)obs_dev & 7u) != 0 || ((uintptr_t)act_out_dev & 15u) != 0 ||
         ((uintptr_t)packed_dev & 15u) != 0)
         return CF2_ERR_INVALID_ARG;
     if (final_obs_dev && ((uintptr_t)final_obs_dev & 7u) != 0) return CF2_ERR_INVALID_ARG;

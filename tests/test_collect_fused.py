@@ -9,6 +9,9 @@ The collect loop being restated is IWPGAlgorithm.roll_out (algs/iwpg/iwpg.py:372
 import pytest
 import torch
 
+from cf2sim.config import build_config
+from parity_util import N1, copy_config, edit_reward
+
 pytestmark = pytest.mark.gpu
 
 CASES = [
@@ -19,13 +22,19 @@ CASES = [
     ("DroneHoverBulletFreeEnvWithGust-v0", 32768, {}),                                    # the 8-GPU node shard
     ("DroneHoverBulletFreeEnvWithConstWind-v0", 4096, dict(max_episode_steps=9)),         # C2
     ("DroneHoverBulletFreeEnvWithoutAdversary-v0", 5000, dict(domain_randomization=0)),   # partial last block
+    # large N again (appended, so the ids of the cases above stay as they were): collect_kernel with a partial last wave
+    ("DroneHoverBulletFreeEnvWithGust-v0", N1, {}),
 ]
 
 
-def _pair(env_id, n, kw, setup=None, count=2):
+def _pair(env_id, n, kw, setup=None, count=2, config=None):
+    """config: a ready CF2Config (for n envs) that every env gets instead of build_config's."""
     from cf2sim.rollout import FusedActorCritic, MLPActorCritic
     from cf2sim.vec_env import BatchedCrazyflieEnv
-    envs = [BatchedCrazyflieEnv(env_id, n, seed=11, want_final_obs=True, **kw) for _ in range(count)]
+    if config is not None:
+        envs = [BatchedCrazyflieEnv(env_id, n, want_final_obs=True, config=copy_config(config)) for _ in range(count)]
+    else:
+        envs = [BatchedCrazyflieEnv(env_id, n, seed=11, want_final_obs=True, **kw) for _ in range(count)]
     torch.manual_seed(5)
     ac = MLPActorCritic(obs_dim=envs[0].obs_dim).cuda()
     with torch.no_grad():                    # non-trivial standardisation, as after a few epochs
@@ -57,11 +66,11 @@ def _spy(env, name, log):
     setattr(env, name, spy)
 
 
-def _run(env_id, n, kw, setup=None, T=24):
+def _run(env_id, n, kw, setup=None, T=24, config=None):
     """One collect per mode (one launch / one launch per step / two launches per step) from the
     same state; returns the fused calls' support flags (rollout, per-step)."""
     from cf2sim.rollout import collect
-    (ea, pa), (es, ps), (eb, pb) = _pair(env_id, n, kw, setup, count=3)
+    (ea, pa), (es, ps), (eb, pb) = _pair(env_id, n, kw, setup, count=3, config=config)
     oa, os_, ob = ea.reset(), es.reset(), eb.reset()
     launched_roll, launched_step = [], []
     _spy(ea, "collect_rollout_into", launched_roll)
@@ -97,6 +106,14 @@ def _run(env_id, n, kw, setup=None, T=24):
 @pytest.mark.parametrize("env_id,n,kw", CASES)
 def test_fused_collect_equals_two_launches(gpu, env_id, n, kw):
     roll, step = _run(env_id, n, kw)
+    assert roll and all(roll) and step and all(step), "a fused kernel did not run"
+
+
+def test_fused_collect_with_edited_reward(gpu):
+    """Every reward weight and target off its default (several defaults are zero): collect_kernel
+    re-reads them from the kernarg segment (late_epilogue), at N1 with a partial last wave."""
+    env_id = "DroneHoverBulletFreeEnvWithGust-v0"
+    roll, step = _run(env_id, N1, {}, config=edit_reward(build_config(env_id, N1, seed=11)))
     assert roll and all(roll) and step and all(step), "a fused kernel did not run"
 
 

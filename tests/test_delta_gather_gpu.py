@@ -384,11 +384,14 @@ def test_batch_calls_reject_misuse(gpu, tmp_path):
     assert got == [-1, -1, -1, 0, -1, -1, -1, -1, -1, 0, 0], got
 
 
-def test_delta_exchange_one_rccl_rank_batched_run_large_shard(gpu, tmp_path):
+@pytest.mark.parametrize("n", [40000, 33089])
+def test_delta_exchange_one_rccl_rank_batched_run_large_shard(gpu, tmp_path, n):
     """The same above 32 768 envs: the pack fused into step_kernel (256-env blocks, 4 pack blocks
-    each, a ragged last block) instead of step_kernel_small."""
+    each, a ragged last block) instead of step_kernel_small.  33 089 envs: a partial last wave
+    (65 envs in the last block), so pack_epilogue_block takes its scalar copy path and its bitmap
+    guard for a partial wave."""
     out = str(tmp_path / "r.txt")
-    mp.spawn(_run_env, args=(1, _port(), out, "nccl", 40000, 120, "run"), nprocs=1, join=True)
+    mp.spawn(_run_env, args=(1, _port(), out, "nccl", n, 120, "run"), nprocs=1, join=True)
     _check(out, "native", min_checked=8)
 
 

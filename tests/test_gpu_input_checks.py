@@ -50,6 +50,32 @@ def test_step_into_rejects_bad_buffers(gpu):
     env.close()
 
 
+@pytest.mark.parametrize("n", [65, 33089])
+def test_step_into_a_slab_of_an_odd_env_count(gpu, n):
+    """With an odd env count, slab k of contiguous [K, N, obs_dim] rollout storage is 8-byte but not
+    16-byte aligned (N * obs_dim * 4 bytes is an odd multiple of 8): step_into() takes it, and the
+    rows equal those of a step into a 16-byte aligned buffer bit for bit (both kernel families:
+    64- and 256-env blocks, each with a full and a partial block).  A 4-byte aligned buffer is
+    still refused."""
+    from cf2sim.vec_env import BatchedCrazyflieEnv
+    a, b = (BatchedCrazyflieEnv(ENV, n, seed=2) for _ in range(2))
+    a.reset(); b.reset()
+    od = a.obs_dim
+    slabs = torch.zeros(2, n, od, device=gpu)
+    assert slabs[1].data_ptr() % 16 == 8
+    act = torch.rand(n, 4, device=gpu) * 2 - 1
+    ka, kb = _bufs(n, od, gpu), _bufs(n, od, gpu)
+    ka["obs_out"] = slabs[1]
+    a.step_into(act, **ka)
+    b.step_into(act, **kb)
+    assert torch.equal(slabs[1], kb["obs_out"]) and not bool((slabs[0] != 0).any())
+    assert torch.equal(ka["rew_out"], kb["rew_out"]) and torch.equal(ka["done_out"], kb["done_out"])
+    with pytest.raises(ValueError):
+        kb["obs_out"] = torch.zeros(n * od + 1, device=gpu)[1:].view(n, od)
+        b.step_into(act, **kb)
+    a.close(); b.close()
+
+
 def test_boltzmann_env_needs_one_table_per_level(gpu):
     from cf2sim.vec_env import BatchedCrazyflieEnv
     env = BatchedCrazyflieEnv("DroneHoverBulletFreeEnvWithRandomHJAdversary-v0", 64)

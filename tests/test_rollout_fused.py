@@ -6,6 +6,9 @@ import numpy as np
 import pytest
 import torch
 
+from cf2sim.config import build_config
+from parity_util import N1, N4, edit_done, edit_physics, edit_reset, edit_reward
+
 pytestmark = pytest.mark.gpu
 
 CASES = [
@@ -17,11 +20,40 @@ CASES = [
     ("DroneHoverBulletFreeEnvWithoutAdversary-v0", 512, dict(aggregate_phy_steps=1, latency=0.02, max_episode_steps=9)),
     ("DroneHoverBulletFreeEnvWithGust-v0", 150000, {}),       # > one residency round: sliced
 ]
+FREE = "DroneHoverBulletFreeEnvWithoutAdversary-v0"
+# rollout_kernel (above 32 768 envs) with a partial last block and wave, on the instances other
+# than the noisy, domain-randomised default: N1 = 33 089 envs, N4 = 33 092 for the formations
+LARGE_CASES = [
+    (FREE, N1, dict(observation_noise=0, domain_randomization=-1, motor_thrust_noise=0)),
+    ("DroneHoverSimpleEnv-v0", N1, dict(max_episode_steps=7)),
+    (FREE, N1, dict(aggregate_phy_steps=1)),
+    (FREE, N1, dict(latency=0.02, max_episode_steps=7)),
+    ("DroneHoverBulletFreeEnvWithDownwash-v0", N4, {}),
+]
 
 
 @pytest.mark.parametrize("env_id,n,kw", CASES)
 def test_fused_rollout_equals_step_loop(gpu, env_id, n, kw):
     _compare(gpu, env_id, n, kw)
+
+
+@pytest.mark.parametrize("env_id,n,kw", LARGE_CASES)
+def test_fused_rollout_equals_step_loop_large_ragged(gpu, env_id, n, kw):
+    _compare(gpu, env_id, n, kw)
+
+
+def _edited_epilogue(c):
+    return edit_reset(edit_done(edit_reward(c)))
+
+
+@pytest.mark.parametrize("env_id,kw,edit", [
+    ("DroneHoverBulletFreeEnvWithGust-v0", {}, _edited_epilogue),       # late_epilogue, late_reset
+    (FREE, dict(domain_randomization=0), edit_physics),                 # late_physics, late_io
+])
+def test_fused_rollout_with_edited_parameters(gpu, env_id, kw, edit):
+    """Reward weights and targets, done limits, reset limits and (DR off) the physics constants
+    off their defaults: the fused rollout re-reads them from the kernarg segment (LATEX)."""
+    _compare(gpu, env_id, N1, {}, config=edit(build_config(env_id, N1, seed=9, **kw)))
 
 
 @pytest.mark.parametrize("n", [2000, 40000])
@@ -35,9 +67,13 @@ def test_fused_rollout_boltzmann_hj_levels(gpu, n):
              setup=lambda e: e.bind_hj_tables(V, tol))
 
 
-def _compare(gpu, env_id, n, kw, setup=None):
+def _compare(gpu, env_id, n, kw, setup=None, config=None):
+    """config: a ready CF2Config (for n envs) that both envs get instead of build_config's."""
     from cf2sim.vec_env import BatchedCrazyflieEnv
+    from parity_util import copy_config
     K = 24
+    if config is not None:
+        kw = dict(config=copy_config(config))
     a = (torch.rand(K, n, 4, device=gpu, generator=torch.Generator(device=gpu).manual_seed(3)) * 2 - 1).contiguous()
     ref = BatchedCrazyflieEnv(env_id, n, seed=9, want_final_obs=True, **kw)
     fus = BatchedCrazyflieEnv(env_id, n, seed=9, want_final_obs=True, **kw)
