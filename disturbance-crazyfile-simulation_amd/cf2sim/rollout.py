@@ -20,6 +20,11 @@ Reference behaviour restated (paths relative to phoenix_drone_simulation/):
   the statistics are ``OnlineMeanStd`` (utils/online_mean_std.py), updated once per epoch by
   ``update_running_statistics`` (iwpg.py:412-420).  The fused kernel standardises the observation
   in registers before the first layer (pack_policy_weights carries mean and 1 / (std + eps)).
+  ``update_running_statistics(..., device=True)`` takes the batch moments from one pass of a HIP
+  kernel over the rollout (cf2_column_moments) instead of torch's passes.
+* The epoch log's EpRet / EpLen / EpCosts (``logger.store`` at every episode end in roll_out):
+  ``EpisodeStats``, per-env running sums carried across collects and reduced on the device
+  (cf2_episode_stats).
 
 Here N envs run in lock step with on-device auto-reset, so episode boundaries differ per env.
 ``gae`` evaluates the same recursion over a [T, N] buffer with per-env masks:
@@ -105,6 +110,58 @@ class OnlineMeanStd(nn.Module):
         self.count.copy_(n_ab)
         self.std.copy_(torch.sqrt(m2_ab / n_ab))
 
+    @torch.no_grad()
+    def update_from_moments(self, n_b: int, mean_b: torch.Tensor, m2_b: torch.Tensor) -> None:
+        """``update`` from a batch's moments instead of its rows: n_b rows with column means mean_b
+        and M2_b = sum (x - mean_b)^2.  Same arithmetic, including update's batch variance about the
+        *new* mean (the part golden_f3.npz pins), which from moments is
+        (M2_b + n_b (mean_b - mean_new)^2) / n_b.  Evaluated in fp64 (count read into fp64; the fp32
+        count buffer alone would stop counting single rows at 2^24) and rounded once into the fp32
+        buffers; no host synchronisation."""
+        dev = self.mean.device
+        mean_b = torch.as_tensor(mean_b, dtype=torch.float64, device=dev).reshape(self.shape)
+        m2_b = torch.as_tensor(m2_b, dtype=torch.float64, device=dev).reshape(self.shape)
+        n_b = int(n_b)
+        if n_b <= 0:
+            raise ValueError(f"a batch has at least one row, got {n_b}")
+        n_a = self.count.double()
+        n_ab = n_a + n_b
+        mean_a = self.mean.double()
+        delta = mean_b - mean_a
+        mean_new = mean_a + delta * n_b / n_ab
+        batch_var = (m2_b + n_b * torch.square(mean_b - mean_new)) / n_b
+        m2_ab = n_a * torch.square(self.std.double()) + n_b * batch_var + delta ** 2 * (n_a * n_b / n_ab)
+        self.mean.copy_(mean_new)
+        self.count.copy_(n_ab)
+        self.std.copy_(torch.sqrt(m2_ab / n_ab))
+
+    @torch.no_grad()
+    def update_device(self, x: torch.Tensor) -> None:
+        """``update(x)`` for a float32 batch on the GPU in one pass over x: cf2_column_moments
+        (fp64 column means and M2, csrc/cf2sim_stats.hip), then ``update_from_moments``.  x is
+        [B, D] (or [B] for shape (1,) statistics), contiguous; nothing synchronises with the host."""
+        from . import _native
+        dev = self.mean.device
+        d = self.shape[0]
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device != dev or not x.is_contiguous():
+            raise ValueError(f"update_device needs a contiguous float32 tensor on {dev}")
+        if (x.dim() != 1) if d == 1 else (x.dim() != 2 or x.shape[1] != d):
+            raise ValueError(f"expected {'[B]' if d == 1 else f'[B, {d}]'}, got {tuple(x.shape)}")
+        rows = x.shape[0]
+        if rows == 0:
+            raise ValueError("a batch has at least one row, got 0")
+        lib = _native.load()
+        need = lib.cf2_column_moments_scratch_bytes(rows, d)
+        buf = getattr(self, "_moments_buf", None)
+        if buf is None or buf[0].device != dev or buf[0].numel() * 8 < need:
+            buf = (torch.empty((need + 7) // 8, dtype=torch.float64, device=dev),
+                   torch.empty(2 * d, dtype=torch.float64, device=dev))
+            self._moments_buf = buf           # plain attribute: not part of the state dict
+        scratch, out = buf
+        _native.check(lib.cf2_column_moments(x.data_ptr(), rows, d, out.data_ptr(), scratch.data_ptr(),
+                                             torch.cuda.current_stream(dev).cuda_stream), "cf2_column_moments")
+        self.update_from_moments(rows, out[:d], out[d:])
+
 
 class MLPActorCritic(nn.Module):
     """Gaussian MLP policy + MLP value function with the reference's PPO defaults, the
@@ -170,14 +227,19 @@ class MLPActorCritic(nn.Module):
         return torch.distributions.Normal(mu, self.log_std.exp()).log_prob(act).sum(-1)
 
 
-def update_running_statistics(ac: MLPActorCritic, rollout: "Rollout", fused: "FusedActorCritic | None" = None):
+def update_running_statistics(ac: MLPActorCritic, rollout: "Rollout", fused: "FusedActorCritic | None" = None,
+                              device: bool = False):
     """IWPGAlgorithm.update_running_statistics (iwpg.py:412-420) on a whole batched rollout: the raw
     observations update the observation statistics, the discounted returns the return statistics.
-    A FusedActorCritic over `ac` is re-synced (its weight block carries the standardisation)."""
+    A FusedActorCritic over `ac` is re-synced (its weight block carries the standardisation).
+    device=True: both updates read the rollout once through cf2_column_moments
+    (``OnlineMeanStd.update_device``) instead of torch's passes over it."""
     if ac.obs_oms is not None:
-        ac.obs_oms.update(rollout.obs.reshape(-1, rollout.obs.shape[-1]))
+        upd = ac.obs_oms.update_device if device else ac.obs_oms.update
+        upd(rollout.obs.reshape(-1, rollout.obs.shape[-1]))
     if ac.ret_oms is not None:
-        ac.ret_oms.update(rollout.discounted_ret.reshape(-1))
+        upd = ac.ret_oms.update_device if device else ac.ret_oms.update
+        upd(rollout.discounted_ret.reshape(-1))
     if fused is not None:
         fused.sync()
 
@@ -348,6 +410,130 @@ def gae_device(rew, val, done_u8, trunc_u8, last_val, trunc_val, gamma: float = 
     return (adv, ret, disc) if with_discounted else (adv, ret)
 
 
+class EpisodeStats:
+    """The epoch log's EpRet / EpLen / EpCosts (iwpg.py:372-410: roll_out stores them at every
+    episode end, the logger prints mean, std, min and max) for envs that auto-reset on the device:
+    per-env running sums carried from one collect to the next, and a 16-double summary of the
+    episodes that finished (cf2_episode_stats, csrc/cf2sim_stats.hip; layout in include/cf2sim.h).
+    Pass one to ``collect(..., stats=)`` every epoch and read ``summary()`` once per epoch."""
+
+    KEYS = ("EpRet", "EpLen", "EpCosts")      # at raw()[1:5], [5:9], [9:13]: sum, sumsq, min, max
+
+    def __init__(self, num_envs: int, device):
+        from . import _native
+        self.lib = _native.load()
+        self.num_envs = int(num_envs)
+        if self.num_envs <= 0:
+            raise ValueError(f"num_envs must be positive, got {num_envs}")
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        n, dev = self.num_envs, self.device
+        self.ep_ret = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.ep_cost = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.ep_len = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._summary = torch.zeros(16, dtype=torch.float64, device=dev)
+        self._scratch = torch.empty(self.lib.cf2_episode_stats_scratch_bytes(n) // 8, dtype=torch.float64, device=dev)
+        self._all_costs = True                # every update since the last clear was given costs
+
+    def reset(self, mask: torch.Tensor | None = None) -> None:
+        """Forget the running episodes of all envs, or of the masked ones ([N] bool / uint8): call
+        it after an ``envs.reset(...)`` that abandons them.  The summary is kept."""
+        if mask is None:
+            self.ep_ret.zero_(); self.ep_cost.zero_(); self.ep_len.zero_()
+            return
+        m = torch.as_tensor(mask).to(device=self.device).bool()
+        if tuple(m.shape) != (self.num_envs,):
+            raise ValueError(f"mask must have shape ({self.num_envs},), got {tuple(m.shape)}")
+        self.ep_ret.masked_fill_(m, 0.0); self.ep_cost.masked_fill_(m, 0.0); self.ep_len.masked_fill_(m, 0)
+
+    @torch.no_grad()
+    def update(self, rew: torch.Tensor, done: torch.Tensor, cost: torch.Tensor | None = None,
+               ep_ret_out: torch.Tensor | None = None, ep_len_out: torch.Tensor | None = None,
+               ep_cost_out: torch.Tensor | None = None) -> None:
+        """Scan [T, N] (or [N]: one step) rewards, done flags (uint8 or bool) and optional costs
+        forward in time and add the episodes that finished to the running summary.  ep_*_out:
+        optional [T, N] float32 / int32 / float32 buffers that receive a finished episode's return,
+        length and cost in the slot of its last step (other slots are left untouched)."""
+        from . import _native
+        from .vec_env import _check_buf
+        if not isinstance(rew, torch.Tensor) or rew.dim() not in (1, 2):
+            raise ValueError("rew must be a [T, N] or [N] torch tensor")
+        shape = (1, self.num_envs) if rew.dim() == 1 else (rew.shape[0], self.num_envs)
+        flat = rew.dim() == 1
+        if isinstance(done, torch.Tensor) and done.dtype == torch.bool:
+            done = done.view(torch.uint8)        # same bytes (0 / 1), no copy
+        bufs = {"rew": (rew, torch.float32), "done": (done, torch.uint8), "cost": (cost, torch.float32),
+                "ep_ret_out": (ep_ret_out, torch.float32), "ep_len_out": (ep_len_out, torch.int32),
+                "ep_cost_out": (ep_cost_out, torch.float32)}
+        for name, (t, dt) in bufs.items():
+            if t is None and name in ("rew", "done"):
+                raise ValueError(f"{name} is required")
+            _check_buf(t, name, shape[1:] if flat else shape, dt, self.device, align=1 if dt == torch.uint8 else 4)
+        if shape[0] == 0:
+            return
+        _native.check(self.lib.cf2_episode_stats(
+            shape[0], shape[1], rew.data_ptr(), _native.ptr(cost), done.data_ptr(), self.ep_ret.data_ptr(),
+            self.ep_cost.data_ptr(), self.ep_len.data_ptr(), _native.ptr(ep_ret_out), _native.ptr(ep_len_out),
+            _native.ptr(ep_cost_out), self._summary.data_ptr(), 1, self._scratch.data_ptr(),
+            torch.cuda.current_stream(self.device).cuda_stream), "cf2_episode_stats")
+        self._all_costs = self._all_costs and cost is not None
+
+    def raw(self) -> torch.Tensor:
+        """The 16-double device summary (a copy): what ranks gather for ``merge_raw``."""
+        return self._summary.clone()
+
+    @staticmethod
+    def merge_raw(raws) -> torch.Tensor:
+        """Combine summaries (CPU tensors or arrays of 16 doubles, e.g. every rank's ``raw()``):
+        counts and sums add, minima and maxima combine, a summary with count 0 is ignored."""
+        import numpy as np
+        out = np.zeros(16)
+        out[[3, 7, 11]], out[[4, 8, 12]] = np.inf, -np.inf
+        for r in raws:
+            r = np.asarray(r.detach().cpu() if isinstance(r, torch.Tensor) else r, dtype=np.float64).reshape(-1)
+            if r.shape != (16,):
+                raise ValueError(f"a raw summary has 16 entries, got {r.shape}")
+            if not r[0] > 0:
+                continue
+            out[0] += r[0]
+            for k in (1, 5, 9):
+                out[k] += r[k]
+                out[k + 1] += r[k + 1]
+                out[k + 2] = min(out[k + 2], r[k + 2])
+                out[k + 3] = max(out[k + 3], r[k + 3])
+        return torch.from_numpy(out)
+
+    @staticmethod
+    def summary_of(raw, with_costs: bool = True) -> dict:
+        """The log entries of a raw summary: ``episodes`` and, per key, mean / std / min / max (the
+        population std, as the reference's logger computes it; NaN mean and std with no episode)."""
+        import numpy as np
+        r = np.asarray(raw.detach().cpu() if isinstance(raw, torch.Tensor) else raw, dtype=np.float64).reshape(-1)
+        cnt = r[0] if r[0] > 0 else 0.0
+        out = {"episodes": int(cnt)}
+        for key, k in zip(EpisodeStats.KEYS, (1, 5, 9)):
+            if key == "EpCosts" and not with_costs:
+                continue
+            if cnt > 0:
+                mean = r[k] / cnt
+                std = math.sqrt(max(r[k + 1] / cnt - mean * mean, 0.0))
+                out[key] = {"mean": mean, "std": std, "min": float(r[k + 2]), "max": float(r[k + 3])}
+            else:
+                out[key] = {"mean": math.nan, "std": math.nan, "min": math.inf, "max": -math.inf}
+        return out
+
+    def summary(self, clear: bool = True) -> dict:
+        """Synchronise and return the finished episodes' statistics since the last clear (episodes
+        still running are not counted).  ``EpCosts`` is present only if every update since then was
+        given costs.  clear=True empties the summary; the per-env carries stay."""
+        out = self.summary_of(self._summary.cpu(), with_costs=self._all_costs)
+        if clear:
+            self._summary.zero_()
+            self._all_costs = True
+        return out
+
+
 @dataclasses.dataclass
 class Rollout:
     obs: torch.Tensor        # [T, N, obs_dim]
@@ -382,7 +568,7 @@ def _fused_storage(steps: int, n: int, d: int, dev) -> dict:
 @torch.no_grad()
 def collect(envs, ac, steps: int, obs: torch.Tensor | None = None, gamma: float = 0.99,
             lam: float = 0.95, generator: torch.Generator | None = None, fuse: bool | str = True,
-            out: Rollout | None = None) -> Rollout:
+            out: Rollout | None = None, stats: EpisodeStats | None = None) -> Rollout:
     """``roll_out`` for all envs of a BatchedCrazyflieEnv at once; everything stays on the GPU.
     ``ac`` is an MLPActorCritic (torch layers) or a FusedActorCritic (HIP kernels).  With a
     FusedActorCritic, ``fuse`` picks how the loop's env-steps and policy calls are launched where
@@ -393,11 +579,16 @@ def collect(envs, ac, steps: int, obs: torch.Tensor | None = None, gamma: float 
     ``out``: a Rollout of an earlier fused collect of the
     same shape whose storage is re-used (its tensors are overwritten; ``obs=out.last_obs`` is
     allowed), as a training loop collecting every epoch would.
+    ``stats``: an EpisodeStats that follows the envs' episodes through this collect (reset with
+    the envs when ``obs`` is None, then updated from the rollout's rewards and done flags; the
+    torch-module path also hands it the per-step costs, the fused kernels write none).
     ``envs`` must have been created with want_final_obs=True (time-out bootstrapping)."""
     if envs.final_obs is None:
         raise ValueError("collect() needs BatchedCrazyflieEnv(..., want_final_obs=True)")
     n, d, dev = envs.num_envs, envs.obs_dim, envs.device
     o = envs.reset() if obs is None else obs
+    if stats is not None and obs is None:
+        stats.reset()
     fused = isinstance(ac, FusedActorCritic)
     module = ac.ac if fused else ac
     rew_den = module.ret_oms.std_host() + module.ret_oms.eps if module.ret_oms is not None else None
@@ -449,6 +640,8 @@ def collect(envs, ac, steps: int, obs: torch.Tensor | None = None, gamma: float 
         adv, ret, disc = gae_device(buf_r, buf_v, d8, tr8, last_val, trunc_val, gamma, lam, rew_den, True,
                                     out=(S["adv"], S["ret"], S["disc"]))
         buf_o, buf_d, buf_tr = obs_buf[:steps], d8.view(torch.bool), tr8.view(torch.bool)   # 0/1 bytes
+        if stats is not None:
+            stats.update(buf_r, d8)           # no cost: cf2_collect_step has no cost output
         return Rollout(buf_o, buf_a, buf_r, buf_v, buf_lp, buf_d, buf_tr, adv, ret, o, last_val, trunc_val, disc,
                        storage=S)
     buf_o = torch.empty(steps, n, d, device=dev)
@@ -459,6 +652,7 @@ def collect(envs, ac, steps: int, obs: torch.Tensor | None = None, gamma: float 
     buf_d = torch.empty(steps, n, dtype=torch.bool, device=dev)
     buf_tr = torch.empty(steps, n, dtype=torch.bool, device=dev)
     trunc_val = torch.zeros(steps, n, device=dev)
+    buf_c = torch.empty(steps, n, device=dev) if stats is not None else None
     for t in range(steps):
         a, v, lp = ac.step(o, generator=generator)
         buf_o[t] = o
@@ -469,11 +663,15 @@ def collect(envs, ac, steps: int, obs: torch.Tensor | None = None, gamma: float 
         buf_r[t] = r
         buf_d[t] = dn.bool()
         buf_tr[t] = info["truncated"].bool()
+        if buf_c is not None:
+            buf_c[t] = info["cost"]
         trunc_val[t] = ac.value(info["final_obs"])      # only read where truncated
     last_val = ac.value(o)
     adv, ret, disc = gae(buf_r, buf_v, buf_d, buf_tr, last_val, trunc_val, gamma, lam, rew_den, True)
+    if stats is not None:
+        stats.update(buf_r, buf_d, buf_c)
     return Rollout(buf_o, buf_a, buf_r, buf_v, buf_lp, buf_d, buf_tr, adv, ret, o, last_val, trunc_val, disc)
 
 
 __all__ = ["OnlineMeanStd", "MLPActorCritic", "FusedActorCritic", "pack_policy_weights", "gae", "gae_device", "collect",
-           "Rollout", "update_running_statistics"]
+           "Rollout", "update_running_statistics", "EpisodeStats"]

@@ -338,6 +338,39 @@ int  cf2_gae(uint32_t T, uint32_t n, const float* rew_dev, const float* val_dev,
              const uint8_t* trunc_dev, const float* trunc_val_dev, const float* last_val_dev, float gamma,
              float lam, float rew_den, float* adv_dev, float* ret_dev, float* disc_ret_dev, void* stream);
 
+/* Episode statistics over [T, n] rollout buffers (algs/iwpg/iwpg.py:372-410: roll_out keeps ep_ret,
+ * ep_costs and ep_len and stores EpRet / EpLen / EpCosts at every episode end; the epoch log prints
+ * their mean, std, min and max).  The envs auto-reset on the device and an episode outlasts a
+ * collect, so the running sums are per-env carries (carry_ret f32, carry_cost f32, carry_len int32,
+ * [n] each, updated in place; zero them where an episode is abandoned).  Per step t, in time order:
+ * carry_ret += rew[t], carry_cost += cost[t] (cost_dev NULL: 0), ++carry_len, plain f32 / int adds;
+ * where done[t] != 0 (terminal or time-out) the episode ends including step t: its three values go
+ * to slot [t, env] of the optional ep_*_out buffers ([T, n]; other slots are left untouched) and
+ * into the summary, and the carry restarts at 0.  summary_dev, 16 doubles: [0] episodes finished,
+ * [1..4] return sum, sum of squares, min, max, [5..8] length, [9..12] cost, [13..15] 0; with no
+ * episode min = +inf and max = -inf.  accumulate != 0 merges this call into the summary already
+ * there (one whose count is 0 is empty whatever else it holds); 0 overwrites.  scratch_dev:
+ * cf2_episode_stats_scratch_bytes(n) bytes, 8-byte aligned.  Two launches on `stream`; no atomics,
+ * the same input gives the same bits.  T == 0 or n == 0: CF2_OK, nothing launched. */
+size_t cf2_episode_stats_scratch_bytes(uint32_t n);
+int  cf2_episode_stats(uint32_t T, uint32_t n, const float* rew_dev, const float* cost_dev, const uint8_t* done_dev,
+                       float* carry_ret_dev, float* carry_cost_dev, int32_t* carry_len_dev, float* ep_ret_out_dev,
+                       int32_t* ep_len_out_dev, float* ep_cost_out_dev, double* summary_dev, int accumulate,
+                       void* scratch_dev, void* stream);
+
+/* Column moments of a dense row-major [rows, D] f32 matrix, 1 <= D <= 64, read once: out_dev gets
+ * mean[D], then M2[D] = sum over rows of (x - mean)^2, in fp64 -- the batch moments the running
+ * statistics (utils/online_mean_std.py; update_running_statistics, iwpg.py:412-420) are updated
+ * from.  Sums are fp64 and shifted by a row of the matrix, block partials (count, mean, M2) are
+ * merged in index order (Chan et al.): M2 >= 0, exactly 0 for a constant column, and the same input
+ * gives the same bits.  x_dev is 4-byte aligned; a 16-byte (8-byte) aligned one streams with
+ * 16-byte (8-byte) loads, whatever D.  scratch_dev:
+ * cf2_column_moments_scratch_bytes(rows, D) bytes, 8-byte aligned.  D == 0 or D > 64:
+ * CF2_ERR_INVALID_ARG; rows == 0: CF2_OK, nothing launched or written. */
+size_t cf2_column_moments_scratch_bytes(uint64_t rows, uint32_t D);
+int  cf2_column_moments(const float* x_dev, uint64_t rows, uint32_t D, double* out_dev, void* scratch_dev,
+                        void* stream);
+
 /* Multi-GPU observation exchange as deltas (the north star's per-step RCCL
  * all-gather of the obs slab).  The reference has no counterpart: its MPI ranks exchange only
  * gradients and statistics (utils/mpi_tools.py:30-44); the rows materialised here are exactly what
