@@ -11,7 +11,7 @@ SRC_DIR = os.path.abspath(os.path.join(PKG_DIR, "..", "csrc"))
 INC_DIR = os.path.abspath(os.path.join(PKG_DIR, "..", "..", "include"))
 LIB = os.path.join(PKG_DIR, "libcf2sim.so")
 SOURCES = ["cf2sim_kernels.hip", "cf2sim_policy.hip", "cf2sim_util.hip", "cf2sim_exchange.hip", "cf2sim_stats.hip",
-           "cf2sim_api.cpp"]
+           "cf2sim_ppo.hip", "cf2sim_api.cpp"]
 # every header of csrc/ is part of every object's content key: one left out would let a stale
 # library pass for up to date
 HEADERS = sorted(f for f in os.listdir(SRC_DIR) if f.endswith(".h"))
@@ -33,7 +33,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp
 # no measured cost (262 144 envs 36.08-36.19 vs 36.06-36.13 us, 32 768 envs within noise).
 SOURCE_FLAGS = {"cf2sim_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=on"], "cf2sim_api.cpp": ["-fno-slp-vectorize"],
                 "cf2sim_policy.hip": ["-fno-slp-vectorize", "-ffp-contract=on"],
-                "cf2sim_stats.hip": ["-ffp-contract=off"]}
+                "cf2sim_stats.hip": ["-ffp-contract=off"],
+                "cf2sim_ppo.hip": ["-fno-slp-vectorize", "-ffp-contract=on"]}
 # The policy TU contracts like the env kernels too: the fused collect kernel (cf2sim_kernels.hip)
 # runs the same policy code (cf2sim_policy.h), and with "fast" the policy kernel alone fused the
 # standardisation's product into the hi/lo split's subtraction (8 v_fma instead of v_sub), so the

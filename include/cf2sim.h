@@ -371,6 +371,46 @@ size_t cf2_column_moments_scratch_bytes(uint64_t rows, uint32_t D);
 int  cf2_column_moments(const float* x_dev, uint64_t rows, uint32_t D, double* out_dev, void* scratch_dev,
                         void* stream);
 
+/* Loss and gradient of the PPO update (algs/ppo/ppo.py compute_loss_pi without the entropy term,
+ * which is constant in the trained parameters: log_std has requires_grad=False; and the critic's mean
+ * squared error of algs/iwpg/iwpg.py), one fused launch per network plus a merge launch.
+ * weights_dev is the flat block of cf2_policy_pack's input (cf2_policy_weights_count(obs_dim) floats),
+ * not the packed one: the optimiser owns the flat values and grad_dev comes back in that layout.
+ * obs_dim 34 or 42; the observation is standardised as in the forward, (obs - mean) * scale.
+ * Rows: obs [n, obs_dim] (8-byte aligned), act [n, 4] (16-byte aligned), logp_old, adv, target [n].
+ * idx_dev: m row indices, each < n, repeats allowed (a value mini-batch); NULL: rows 0..m-1, m <= n.
+ * Policy, per selected row j: mu = pi(z), logp = sum_k -((a_k - mu_k) / sigma_k)^2 / 2 - log sigma_k
+ * - log(2 pi) / 2, ratio = exp(logp - logp_old), L_j = -min(ratio A, clamp(ratio, 1 - c, 1 + c) A),
+ * loss = mean L_j.  A = adv, or with adv_moments_dev ({mean, M2} over the n advantages, as
+ * cf2_column_moments(adv, n, 1, ...) writes them) A = (adv - mean) / (sqrt(M2 / n) + 1e-8), in fp64
+ * and rounded to fp32: the standardisation of the reference's buffer get().  d L_j / d logp is
+ * -A ratio where the unclipped term is the minimum or the ratio is inside the clip range, else 0;
+ * ReLU' is 0 at a pre-activation <= 0.  mu_old_dev [n, 4] (optional) enables the exact Gaussian KL,
+ * KL_j = sum_k (mu_old_k - mu_k)^2 / (2 sigma_k^2).  Value: v = V(z), loss = mean (v - target)^2.
+ * Optional outputs, dense by position j: mu_out [m, 4], logp_out [m], val_out [m].
+ * grad_dev: the policy call writes exactly the words [P_W1, P_LOGSTD) of the flat layout (pi W1 b1
+ * W2 b2 W3 b3), the value call exactly [V_W1, O_MEAN) (v W1 b1 W2 b2 W3 b3); every other word is
+ * left untouched.  NULL: evaluate only (no backward pass), same summary bits.
+ * summary_dev, 8 doubles.  Policy: [0] m, [1] loss, [2] mean(logp_old - logp), [3] share of rows
+ * with |ratio - 1| > c, [4] mean exact KL (0 without mu_old), [5] mean ratio, [6..7] 0.  Value: [0] m,
+ * [1] loss, rest 0.
+ * Products are exact fp32 (v_mfma_f32_16x16x4_f32 and fmaf).  Block partials go to scratch_dev
+ * (cf2_ppo_scratch_bytes(m, obs_dim) bytes, 8-byte aligned; 0 for an unsupported obs_dim) and are
+ * merged in block-index order in fp64, divided by m and rounded once: no atomics, the same input
+ * gives the same bits.  obs_dim not 34 or 42: CF2_ERR_UNSUPPORTED; m == 0: CF2_OK, nothing launched
+ * or written; a NULL required pointer (weights, the row inputs, summary, scratch), a misaligned
+ * pointer, n == 0 or idx_dev == NULL with m > n: CF2_ERR_INVALID_ARG.  Every error returns before
+ * anything is launched. */
+size_t cf2_ppo_scratch_bytes(uint32_t m, uint32_t obs_dim);
+int  cf2_ppo_policy_grad(const float* weights_dev, uint32_t obs_dim, const float* obs_dev, const float* act_dev,
+                         const float* logp_old_dev, const float* adv_dev, uint32_t n, const uint32_t* idx_dev,
+                         uint32_t m, const double* adv_moments_dev, float clip_ratio, const float* mu_old_dev,
+                         float* mu_out_dev, float* logp_out_dev, float* grad_dev, double* summary_dev,
+                         void* scratch_dev, void* stream);
+int  cf2_ppo_value_grad(const float* weights_dev, uint32_t obs_dim, const float* obs_dev, const float* target_dev,
+                        uint32_t n, const uint32_t* idx_dev, uint32_t m, float* val_out_dev, float* grad_dev,
+                        double* summary_dev, void* scratch_dev, void* stream);
+
 /* Multi-GPU observation exchange as deltas (the north star's per-step RCCL
  * all-gather of the obs slab).  The reference has no counterpart: its MPI ranks exchange only
  * gradients and statistics (utils/mpi_tools.py:30-44); the rows materialised here are exactly what
