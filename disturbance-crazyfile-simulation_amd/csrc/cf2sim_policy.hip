@@ -195,6 +195,9 @@ __global__ void __launch_bounds__(PB, POLICY_WAVES) policy_kernel(const float* _
     }
 }
 
+// Mirrored by policy_geometry() in tests/test_policy_gae_edges.py (blocks = min(ceil(n / 128),
+// 2 * CUs), wave w runs chunks w, w + nwaves, ...): a change here must be made there too, or the
+// tests stop knowing which rows run which trip of the chunk loop.
 static int policy_grid(uint32_t n) {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
