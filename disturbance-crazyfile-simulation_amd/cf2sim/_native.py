@@ -22,7 +22,7 @@ REPO_INCLUDE = os.path.abspath(os.path.join(PKG_DIR, "..", "..", "include", "cf2
 # every symbol include/cf2sim.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
     "cf2_abi_version", "cf2_config_sizeof", "cf2_status_string", "cf2_last_hip_error", "cf2_device_errors",
-    "cf2_create", "cf2_destroy", "cf2_layout_get", "cf2_bind_hj_tables", "cf2_reset", "cf2_step", "cf2_collect_step",
+    "cf2_create", "cf2_destroy", "cf2_layout_get", "cf2_store_policy", "cf2_store_policy_for", "cf2_bind_hj_tables", "cf2_reset", "cf2_step", "cf2_collect_step",
     "cf2_collect_rollout", "cf2_physics_step",
     "cf2_set_ground_effect",
     "cf2_rollout", "cf2_get_state", "cf2_set_state", "cf2_hj_disturbance",
@@ -46,6 +46,8 @@ class CF2Layout(ctypes.Structure):
 
 
 CF2_ERR_UNSUPPORTED = -4      # include/cf2sim.h cf2_status
+# include/cf2sim.h CF2_STORE_*: the cache policy of a store (cf2_store_policy)
+STORE_PLAIN, STORE_NT, STORE_WT, STORE_NT_WT = 0, 2, 16, 18
 
 
 class CF2Error(RuntimeError):
@@ -76,6 +78,8 @@ def load() -> ctypes.CDLL:
     lib.cf2_destroy.argtypes = [vp]
     lib.cf2_device_errors.argtypes = [vp, P(ctypes.c_uint32), ctypes.c_int]
     lib.cf2_layout_get.argtypes = [vp, P(CF2Layout)]
+    lib.cf2_store_policy.argtypes = [vp, P(ctypes.c_uint32)]
+    lib.cf2_store_policy_for.argtypes = [P(CF2Config), ctypes.c_char_p, P(ctypes.c_uint32)]
     lib.cf2_bind_hj_tables.argtypes = [vp, vp, ctypes.c_int, P(ctypes.c_int32)]
     lib.cf2_reset.argtypes = [vp, vp, vp, vp]
     lib.cf2_step.argtypes = [vp] * 11
@@ -157,3 +161,19 @@ def check(status: int, what: str = "cf2 call"):
 def ptr(t) -> int | None:
     """Device pointer of a torch tensor (None passes NULL)."""
     return None if t is None else t.data_ptr()
+
+
+def store_policy(ctx) -> tuple:
+    """(state, obs, out) store policy a context runs (cf2_store_policy; STORE_* values)."""
+    out = (ctypes.c_uint32 * 3)()
+    check(load().cf2_store_policy(ctx, out), "cf2_store_policy")
+    return tuple(out)
+
+
+def store_policy_for(cfg, text=None) -> tuple:
+    """(state, obs, out) cf2_create would pick for cfg under `text` (None: CF2SIM_STORE_POLICY of the
+    environment); needs no device.  Raises CF2Error for an unknown or uncompiled policy."""
+    out = (ctypes.c_uint32 * 3)()
+    t = None if text is None else text.encode()
+    check(load().cf2_store_policy_for(ctypes.byref(cfg), t, out), "cf2_store_policy_for")
+    return tuple(out)

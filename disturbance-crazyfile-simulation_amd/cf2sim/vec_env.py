@@ -120,6 +120,8 @@ class BatchedCrazyflieEnv:
         lay = _native.CF2Layout()
         _native.check(self.lib.cf2_layout_get(self._ctx, ctypes.byref(lay)), "cf2_layout_get")
         self.layout = lay
+        # (state, obs, out) cache policy of the context's stores (_native.STORE_*; CF2SIM_STORE_POLICY)
+        self.store_policy = _native.store_policy(self._ctx)
         n, d = self.num_envs, self.device
         self.obs = torch.zeros(n, self.obs_dim, dtype=torch.float32, device=d)
         self.rew = torch.zeros(n, dtype=torch.float32, device=d)

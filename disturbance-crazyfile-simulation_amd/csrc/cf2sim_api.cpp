@@ -5,6 +5,7 @@
 // cf2_reset can be captured into a hipGraph by the caller.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 #include <new>
 
@@ -77,6 +78,67 @@ static uint64_t step_bytes_per_env(const cf2_config* c) {
 // Cache is 256 MB; measured on the bench workload, 327 680 envs (250 MB) run faster with plain
 // stores and 393 216 envs (300 MB) with nt stores (profiles/r03_ab_nt_threshold.txt)
 static const uint64_t NT_STATE_BYTES = 240ull << 20;
+
+// ---- store policy (cf2sim_internal.h) ----
+// The automatic choice, by regime:
+//   N <= SMALL_N_MAX             the small-N kernels, compiled with one policy: plain state, nt obs rows
+//   working set <= NT_STATE_BYTES the state stays in the Infinity Cache between env-steps: write-through
+//                                 state stores and obs rows (every run below every plain run, medians:
+//                                 65 536 envs 13.46 -> 12.62 us, 262 144 envs 33.40 -> 32.89 us)
+//   beyond                        nt state stores (write-through at 1 Mi envs: 138 -> 175 us)
+// A candidate of profiles/store_policy_ab.txt replaced a regime's entry only where every run of
+// its beat every run of the plain policy; the fallback is plain state, nt obs rows, plain outputs.
+StorePolicy cf2::choose_store_policy(uint32_t num_envs, uint64_t step_bytes) {
+    if (num_envs <= SMALL_N_MAX) return StorePolicy{AUX_PLAIN, AUX_NT, AUX_PLAIN};
+    if ((uint64_t)num_envs * step_bytes <= NT_STATE_BYTES) return StorePolicy{AUX_WT, AUX_NT_WT, AUX_PLAIN};
+    return StorePolicy{AUX_NT, AUX_NT, AUX_PLAIN};
+}
+
+static bool parse_aux(const char* s, size_t n, uint32_t* out) {
+    static const struct { const char* name; uint32_t aux; } names[] = {
+        {"plain", AUX_PLAIN}, {"wt", AUX_WT}, {"nt", AUX_NT}, {"nt_wt", AUX_NT_WT}};
+    for (const auto& e : names)
+        if (strlen(e.name) == n && memcmp(e.name, s, n) == 0) { *out = e.aux; return true; }
+    return false;
+}
+
+bool cf2::parse_store_policy(const char* text, StorePolicy* out, bool* is_auto) {
+    *is_auto = false;
+    *out = StorePolicy{AUX_PLAIN, AUX_NT, AUX_PLAIN};
+    if (!text || !*text || strcmp(text, "auto") == 0) { *is_auto = true; return true; }
+    if (strcmp(text, "plain") == 0) return true;
+    if (strcmp(text, "wt") == 0) { *out = StorePolicy{AUX_WT, AUX_NT_WT, AUX_PLAIN}; return true; }
+    if (strcmp(text, "nt") == 0) { *out = StorePolicy{AUX_NT, AUX_NT, AUX_PLAIN}; return true; }
+    // state=P,obs=P,out=P: any subset, each part once
+    unsigned seen = 0;
+    for (const char* p = text;;) {
+        const char* eq = strchr(p, '=');
+        if (!eq) return false;
+        const char* end = strchr(eq, ',');
+        const size_t kn = (size_t)(eq - p), vn = end ? (size_t)(end - eq - 1) : strlen(eq + 1);
+        uint32_t* dst = nullptr;
+        unsigned bit = 0;
+        if (kn == 5 && memcmp(p, "state", 5) == 0) { dst = &out->state; bit = 1u; }
+        else if (kn == 3 && memcmp(p, "obs", 3) == 0) { dst = &out->obs; bit = 2u; }
+        else if (kn == 3 && memcmp(p, "out", 3) == 0) { dst = &out->out; bit = 4u; }
+        if (!dst || (seen & bit) || !parse_aux(eq + 1, vn, dst)) return false;
+        seen |= bit;
+        if (!end) return true;
+        p = end + 1;
+    }
+}
+
+// the policy cf2_create gives a context of this configuration under `text` (NULL: the environment)
+static int resolve_store_policy(const cf2_config* c, const char* text, StorePolicy* sp) {
+    if (!text) text = getenv("CF2SIM_STORE_POLICY");
+    bool is_auto = false;
+    if (!parse_store_policy(text, sp, &is_auto)) return CF2_ERR_INVALID_ARG;
+    const StorePolicy chosen = choose_store_policy(c->num_envs, step_bytes_per_env(c));
+    // the small-N kernels have one compiled policy, whatever was asked for
+    if (is_auto || c->num_envs <= SMALL_N_MAX) *sp = chosen;
+    if (!store_policy_compiled(store_policy_pack(sp->state, sp->obs, sp->out))) return CF2_ERR_UNSUPPORTED;
+    return CF2_OK;
+}
 
 static void fill_tables(const cf2_config* c, KTables& T) {
     memset(&T, 0, sizeof(T));
@@ -186,7 +248,7 @@ static void fill_params(const cf2_config* c, KParams& P) {
     P.tab = nullptr;
     P.V = nullptr;
     P.hj_bits = nullptr;
-    P.nt_state = (uint64_t)c->num_envs * step_bytes_per_env(c) > NT_STATE_BYTES ? 1u : 0u;
+    P.store_policy = POL_DEFAULT;       // cf2_create resolves the context's (resolve_store_policy)
 }
 
 extern "C" {
@@ -216,6 +278,12 @@ int cf2_create(const cf2_config* cfg, cf2_ctx** out_ctx) {
     if (!ctx) return CF2_ERR_OUT_OF_MEMORY;
     ctx->cfg = *cfg;
     fill_params(cfg, ctx->P);
+    {
+        StorePolicy sp;
+        const int r = resolve_store_policy(cfg, nullptr, &sp);
+        if (r) { delete ctx; return r; }
+        ctx->P.store_policy = store_policy_pack(sp.state, sp.obs, sp.out);
+    }
     fill_tables(cfg, ctx->T);
     {   // the reset-only parameters the kernels read from the device tables
         KTables& T = ctx->T;
@@ -265,6 +333,24 @@ int cf2_device_errors(cf2_ctx* ctx, uint32_t* flags_out, int clear) {
     if (e == hipSuccess) e = hipMemcpy(flags_out, dev, sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (e == hipSuccess && clear && *flags_out) e = hipMemset(dev, 0, sizeof(uint32_t));
     return e == hipSuccess ? CF2_OK : hip_fail(e);
+}
+
+int cf2_store_policy(const cf2_ctx* ctx, uint32_t* out3) {
+    if (!ctx || !out3) return CF2_ERR_INVALID_ARG;
+    const uint32_t p = ctx->P.store_policy;
+    out3[0] = p & 0xffu; out3[1] = (p >> 8) & 0xffu; out3[2] = (p >> 16) & 0xffu;
+    return CF2_OK;
+}
+
+int cf2_store_policy_for(const cf2_config* cfg, const char* text, uint32_t* out3) {
+    if (!out3) return CF2_ERR_INVALID_ARG;
+    const int v = validate(cfg);
+    if (v) return v;
+    StorePolicy sp;
+    const int r = resolve_store_policy(cfg, text, &sp);
+    if (r) return r;
+    out3[0] = sp.state; out3[1] = sp.obs; out3[2] = sp.out;
+    return CF2_OK;
 }
 
 int cf2_layout_get(const cf2_ctx* ctx, cf2_layout* o) {

@@ -79,6 +79,28 @@ enum { DSTB_NONE_T = 0, DSTB_EXTERNAL_T = 1, DSTB_UNIFORM_T = 2, DSTB_CONST_T = 
 enum { LEVEL_FIXED_T = 0, LEVEL_BOLTZMANN_T = 1 };
 enum : uint32_t { TAG_STEP = 1, TAG_RESET = 2, TAG_PHYS = 3 };
 
+// Cache policy of a vector store: the aux (cpol) bits of the gfx950 buffer / global stores.
+//   plain  write-back in the XCD's L2 (written to memory when evicted or at the kernel's end)
+//   nt     streamed past the Infinity Cache
+//   wt     sc1: the line stays in L2 and the Infinity Cache, the data goes out as it is stored
+//   nt_wt  both bits
+// A context's policy names one value each for the state stores (step, reset), the obs-row
+// write-out and the per-env outputs (rew, done, trunc, cost, level, direct final_obs rows), packed
+// into KParams::store_policy as state | obs << 8 | out << 16.
+enum : uint32_t { AUX_PLAIN = 0, AUX_NT = 2, AUX_WT = 16, AUX_NT_WT = 18 };
+struct StorePolicy { uint32_t state, obs, out; };
+__host__ __device__ constexpr uint32_t store_policy_pack(uint32_t state, uint32_t obs, uint32_t out) {
+    return state | obs << 8 | out << 16;
+}
+constexpr uint32_t POL_DEFAULT = store_policy_pack(AUX_PLAIN, AUX_NT, AUX_PLAIN);   // plain state, nt obs rows
+// Host side (cf2sim_api.cpp): "auto" | "plain" | "wt" | "nt" | "state=..,obs=..,out=.." (each
+// plain | wt | nt | nt_wt) into *out; false for anything else.  `is_auto` tells the chooser to run.
+bool parse_store_policy(const char* text, StorePolicy* out, bool* is_auto);
+// the automatic choice: env count and bytes one env-step moves per env (step_bytes_per_env)
+StorePolicy choose_store_policy(uint32_t num_envs, uint64_t step_bytes);
+// whether the large-N kernels have an instance for the policy (launch table, cf2sim_kernels.hip)
+bool store_policy_compiled(uint32_t packed);
+
 // Kernel parameter block, passed by value (kernarg segment -> scalar loads).
 struct KParams {
     uint32_t N, gid_off, key0, key1;
@@ -86,9 +108,9 @@ struct KParams {
     uint32_t out_stride;          // rollout kernel: rows per per-step output slab (set per launch)
     // host-side, set once at cf2_create for the context's device and configuration: blocks
     // resident at once of the large-N step / fused rollout / fused collect kernels and of the
-    // small-N collect rollout kernel (query_occupancy), and whether the step's working set exceeds the Infinity Cache
-    // (nt state stores)
-    uint32_t rb_step, rb_roll, rb_collect, rb_croll_small, nt_state;
+    // small-N collect rollout kernel (query_occupancy), and the cache policy of the large-N env
+    // kernels' stores (store_policy_pack: which compiled instance runs)
+    uint32_t rb_step, rb_roll, rb_collect, rb_croll_small, store_policy;
     int32_t agg, obs_rate, buf_size, use_latency, use_motor_dyn, max_steps, auto_reset, reset_dist;
     int32_t dstb_mode, level_mode, num_levels, gust_dur, noise, dr, phys, held_persistent, need_level;
     float time_step, mass, ixx, iyy, izz, ft0, ft1, K, A, B, hover_x, hover_action, ou_sigma;

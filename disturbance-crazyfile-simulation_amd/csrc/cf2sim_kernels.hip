@@ -58,7 +58,8 @@ namespace cf2 {
 // End of a block's env-step: list the finished envs (wave ballots into per-wave lists), reset
 // them block-cooperatively (see step_kernel) and write the block's obs rows out coalesced.  Every
 // thread of the block calls it.
-template <bool NOISE, bool DR, int PHYS, uint32_t B, uint32_t C, int TAB = 0>
+// ST_AUX, OBS_AUX: cache policy of the resets' state stores and of the obs write-out (AUX_*).
+template <bool NOISE, bool DR, int PHYS, uint32_t B, uint32_t C, int TAB = 0, int ST_AUX = 0, int OBS_AUX = (int)AUX_NT>
 __device__ __forceinline__ void block_epilogue(const KParams& P, const StepIO& io, uint32_t base, uint32_t tid,
                                                bool do_reset, const ResetSeed& rs, float* s_obs, uint32_t* s_list,
                                                uint32_t* s_rand, uint32_t* s_wcnt) {
@@ -130,7 +131,7 @@ __device__ __forceinline__ void block_epilogue(const KParams& P, const StepIO& i
             // with the block index so the co-resident blocks' roles spread over the SIMDs
             if (act) {
                 const TableRng tg{s_rand + rl, C};
-                reset_role<NOISE, DR, PHYS, TAB>(P, io.sf, base + t, q, tg, s_obs + t * OD, role);
+                reset_role<NOISE, DR, PHYS, TAB, ST_AUX>(P, io.sf, base + t, q, tg, s_obs + t * OD, role);
             }
             __syncthreads();     // the next chunk reuses s_rand
         }
@@ -138,7 +139,7 @@ __device__ __forceinline__ void block_epilogue(const KParams& P, const StepIO& i
     } else {
         __syncthreads();         // every obs row of the block is in LDS
     }
-    write_obs_rows<B, OD, B>(io.obs + (size_t)base * OD, s_obs, P.N - base < B ? P.N - base : B, tid);
+    write_obs_rows<B, OD, B, OBS_AUX>(io.obs + (size_t)base * OD, s_obs, P.N - base < B ? P.N - base : B, tid);
 }
 
 // The delta exchange's pack fused into the large-N env-step (cf2_step_packed above 32 768 envs):
@@ -197,13 +198,18 @@ __device__ __forceinline__ void pack_epilogue_block(const PackIO& X, uint32_t n,
 // compaction group), 3 waves per SIMD (<= 168 VGPRs, <= 53 KB LDS per block); resets drawn and run
 // in chunks of 32
 constexpr uint32_t STEP_BLOCK = 256, STEP_MIN_WAVES = 3, RESET_CHUNK = 32;
+// the parts of a packed store policy (store_policy_pack, cf2sim_internal.h)
+constexpr int pol_state(int pol) { return pol & 0xff; }
+constexpr int pol_obs(int pol) { return (pol >> 8) & 0xff; }
 // Step kernel: one lane per env.  Auto-reset is compacted per block: with random actions a few
 // % of envs finish per step, so nearly every wave would hold one and run the whole reset path
 // divergently.  Finished envs are listed in LDS and reset by the fewest waves after a block
 // barrier; their state rows were just written by this block and are still in L2, so the reset's
 // scattered SoA accesses cost no extra HBM traffic (a separate reset kernel pays ~60 B per
 // 4-byte field access for them).
-template <bool NOISE, bool DR, int PHYS, int SPEC, int ST_AUX = 0>
+// POL: the cache policy of its stores (store_policy_pack: state | obs rows | per-env outputs), a
+// compile-time value per instance; the host picks the instance (launch_step_t).
+template <bool NOISE, bool DR, int PHYS, int SPEC, int POL = (int)POL_DEFAULT>
 __global__ void __launch_bounds__(STEP_BLOCK, STEP_MIN_WAVES) step_kernel(KParams P0, StepIO io, PackIO X) {
     const KParams P = shape_view<SPEC>(P0);
     // Issue priority: the blocks that start only after the first residency round (the partial
@@ -224,8 +230,10 @@ __global__ void __launch_bounds__(STEP_BLOCK, STEP_MIN_WAVES) step_kernel(KParam
     ResetSeed rs;
     __shared__ double s_hjgrid[6 * HJ_PTS];
     if (P.dstb_mode == DSTB_HJ_T) stage_hj_grid(P.tab->hj_grid, s_hjgrid);     // uniform branch
-    if (i < P.N) do_reset = step_env<NOISE, DR, PHYS, false, false, ST_AUX, true>(P, io, i, s_obs + tid * OD, rs, s_hjgrid);
-    block_epilogue<NOISE, DR, PHYS, B, C, 2>(P, io, base, tid, do_reset, rs, s_obs, s_list, s_rand, s_wcnt);
+    if (i < P.N)
+        do_reset = step_env<NOISE, DR, PHYS, false, false, pol_state(POL), true>(P, io, i, s_obs + tid * OD, rs, s_hjgrid);
+    block_epilogue<NOISE, DR, PHYS, B, C, 2, pol_state(POL), pol_obs(POL)>(P, io, base, tid, do_reset, rs, s_obs, s_list,
+                                                                           s_rand, s_wcnt);
     if (X.pk) pack_epilogue_block<NOISE ? 13u : 17u, (uint32_t)OD, B>(X, P.N, base, tid, do_reset, s_obs);
     timing_end();   // resets done
 }
@@ -1373,6 +1381,23 @@ static hipError_t occupancy_t(KParams& P) {
     return hipSuccess;
 }
 
+// The store policies step_kernel is compiled for: the ones choose_store_policy can return
+// (cf2sim_api.cpp; measured in profiles/store_policy_ab.txt).  cf2_create refuses any other
+// (store_policy_compiled).  collect_kernel and rollout_kernel have one form, the plain policy's:
+// with the parameter, write-through did not beat plain in every run (fused rollout 27.24-27.64 vs
+// 26.82-27.53 us per env-step at 262 144 envs; collect 61.1-61.9 vs 62.3-64.3 us there, but
+// 25.98-26.30 vs 25.88-26.30 us at 65 536), so their instances were removed again.
+#define CF2_STORE_POLICIES(X)                                    \
+    X(store_policy_pack(AUX_PLAIN, AUX_NT, AUX_PLAIN))           \
+    X(store_policy_pack(AUX_NT, AUX_NT, AUX_PLAIN))              \
+    X(store_policy_pack(AUX_WT, AUX_NT_WT, AUX_PLAIN))
+bool store_policy_compiled(uint32_t packed) {
+#define CF2_POL_IS(POL) if (packed == (POL)) return true;
+    CF2_STORE_POLICIES(CF2_POL_IS)
+#undef CF2_POL_IS
+    return false;
+}
+
 // blocks of `block` threads (one env or item each) that cover n
 static inline dim3 grid_of(uint32_t n, uint32_t block) { return dim3((n + block - 1) / block); }
 
@@ -1389,14 +1414,16 @@ static hipError_t launch_step_t(const KParams& P, const StepIO& io, hipStream_t 
     const dim3 grid = grid_of(P.N, STEP_BLOCK), block(STEP_BLOCK);
     KParams Pl = P;
     Pl.late_block = P.rb_step;
-    // the env state plus the step's I/O no longer fit the 256 MB Infinity Cache between env-steps
-    // (P.nt_state, cf2_create): stream the state stores past it (nt), HBM-bound regime
-    if (P.nt_state) {
-        hipLaunchKernelGGL((step_kernel<NOISE, DR, PHYS, SPEC, 2>), grid, block, 0, s, Pl, io, X);
-        return hipGetLastError();
+    // the instance of the context's store policy (P.store_policy, cf2_create: e.g. nt state stores
+    // once the env state plus the step's I/O no longer fit the 256 MB Infinity Cache between env-steps)
+#define CF2_POL_LAUNCH(POL)                                                                              \
+    if (P.store_policy == (POL)) {                                                                       \
+        hipLaunchKernelGGL((step_kernel<NOISE, DR, PHYS, SPEC, (int)(POL)>), grid, block, 0, s, Pl, io, X); \
+        return hipGetLastError();                                                                        \
     }
-    hipLaunchKernelGGL((step_kernel<NOISE, DR, PHYS, SPEC>), grid, block, 0, s, Pl, io, X);
-    return hipGetLastError();
+    CF2_STORE_POLICIES(CF2_POL_LAUNCH)
+#undef CF2_POL_LAUNCH
+    return hipErrorNotSupported;
 }
 template <bool NOISE, bool DR, int PHYS, int SPEC>
 static hipError_t launch_collect_t(const KParams& P, const StepIO& io, const PolicyIO& pio, hipStream_t s) {

@@ -288,8 +288,10 @@ __device__ __forceinline__ void reset_one(const KParams& P, float* __restrict__ 
 //   history:    gyro bias (+ gust_left 0), held measurement, action history, o_{k-1} + gyro LPF
 //                                                                        -> groups 10, 14-19, 21-23
 //   params:     domain randomisation, disturbance, level                -> groups 13, 24-27, 29
-template <int PHYS>
-__device__ __forceinline__ void store_reset_kinematics(const KParams& P, const Tile& T, const Env& E, const float ou[4],
+// (TT: the tile type, TileT<ST_AUX>: a kernel's reset stores carry the cache policy of its step stores,
+// so no group of an env is left under two policies in one launch)
+template <int PHYS, class TT>
+__device__ __forceinline__ void store_reset_kinematics(const KParams& P, const TT& T, const Env& E, const float ou[4],
                                                        uint32_t ctr) {
     T.st(0, f4(E.p[0], E.p[1], E.p[2], E.q[0]));
     T.st(1, f4(E.q[1], E.q[2], E.q[3], E.v[0]));
@@ -304,8 +306,8 @@ __device__ __forceinline__ void store_reset_kinematics(const KParams& P, const T
         if (r < P.buf_size) T.st(G_ABUF + r, f4(E.abuf[r][0], E.abuf[r][1], E.abuf[r][2], E.abuf[r][3]));
     if (PHYS == PHYS_SIMPLE_T) T.st(G_RPY, f4(E.rpy[0], E.rpy[1], E.rpy[2], 0.0f));
 }
-template <bool NOISE>
-__device__ __forceinline__ void store_reset_history(const KParams& P, const Tile& T, const Env& E) {
+template <bool NOISE, class TT>
+__device__ __forceinline__ void store_reset_history(const KParams& P, const TT& T, const Env& E) {
     if (NOISE || gust_mode(P))
         T.st(G_BIAS, f4(NOISE ? E.bias[0] : 0.0f, NOISE ? E.bias[1] : 0.0f, NOISE ? E.bias[2] : 0.0f, ib(0)));
     if (NOISE && P.held_persistent) {
@@ -317,8 +319,8 @@ __device__ __forceinline__ void store_reset_history(const KParams& P, const Tile
     T.st(G_HACT + 1, f4(E.hact[1][0], E.hact[1][1], E.hact[1][2], E.hact[1][3]));
     store_obs_prev<NOISE>(T, E);
 }
-template <bool DR>
-__device__ __forceinline__ void store_reset_params(const KParams& P, const Tile& T, const Env& E) {
+template <bool DR, class TT>
+__device__ __forceinline__ void store_reset_params(const KParams& P, const TT& T, const Env& E) {
     if (dstb_stored(P)) T.st(G_DSTB, f4(E.dstb[0], E.dstb[1], E.dstb[2], 0.0f));
     if (DR) {
         T.st(G_PARAM, f4(E.dt, E.m, E.J[0], E.J[1]));
@@ -338,11 +340,11 @@ __device__ __forceinline__ void store_reset_params(const KParams& P, const Tile&
 //   3: domain randomisation, disturbance, level -> store_reset_params
 // Roles 1 and 2 recompute the reset pose from the same table entries, so the critical path is one
 // pose + one sensor call instead of the whole reset.
-template <bool NOISE, bool DR, int PHYS, int TAB = 0>
+template <bool NOISE, bool DR, int PHYS, int TAB = 0, int ST_AUX = 0>
 __device__ __forceinline__ void reset_role(const KParams& P, float* __restrict__ sf, uint32_t i, const ResetSeed& rs,
                                            const TableRng& g, float* __restrict__ obs_row, uint32_t role) {
     constexpr int OL = NOISE ? 13 : 17;
-    const Tile T(sf, P.N, i);
+    const TileT<ST_AUX> T(sf, P.N, i);
     const uint32_t gid = P.gid_off + i;
     Env E;
     TSTAMP(6);   // role start (after the table-draw barrier)

@@ -16,11 +16,30 @@ namespace cf2 {
 // The full-block path is unrolled: every LDS read of the thread's chunks is issued before the first
 // global store, so the chunks pay one LDS round trip instead of one each (the rolled loop waited
 // lgkmcnt(0) before every store: ~3.2k cycles of the small-N env wave for its 9 chunks, r05 timeline).
-template <uint32_t EPB, uint32_t OD, uint32_t NT>
+// OBS_AUX: the stores' cache policy (AUX_*).  AUX_NT is the form above.  AUX_NT_WT adds sc1
+// (write-through: the rows leave the XCD's L2 while the kernel runs instead of at its end; DESIGN.md
+// section 3, "Store cache policy"); such a store goes through a buffer descriptor over the block's
+// rows, the only store whose builtin takes the policy bits (its range check covers exactly the rows
+// written).  obs_chunk_store: chunk k (16 or 8 B) of the block's rows.
+template <int OBS_AUX, class V>
+__device__ __forceinline__ void obs_chunk_store(V* dst, __amdgpu_buffer_rsrc_t r, uint32_t k, V v) {
+    if constexpr (OBS_AUX == (int)AUX_NT) {
+        __builtin_nontemporal_store(v, dst + k);
+    } else if constexpr (sizeof(V) == 16) {
+        typedef unsigned int u4x __attribute__((ext_vector_type(4)));
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4x, v), r, (int)(k * 16u), 0, OBS_AUX);
+    } else {
+        typedef unsigned int u2x __attribute__((ext_vector_type(2)));
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2x, v), r, (int)(k * 8u), 0, OBS_AUX);
+    }
+}
+template <uint32_t EPB, uint32_t OD, uint32_t NT, int OBS_AUX = (int)AUX_NT>
 __device__ __forceinline__ void write_obs_rows(float* dst, const float* s_obs, uint32_t nvalid, uint32_t tid) {
     typedef float f4x __attribute__((ext_vector_type(4)));
     typedef float f2x __attribute__((ext_vector_type(2)));
     constexpr uint32_t epb = EPB, od = OD, nthreads = NT;
+    const __amdgpu_buffer_rsrc_t r =      // (unused, and dropped by the compiler, under AUX_NT)
+        __builtin_amdgcn_make_buffer_rsrc(dst, 0, (int)(nvalid * OD * 4u), 0x00020000);
     if ((EPB * OD) % 4 == 0 && nvalid == epb && ((uintptr_t)dst & 15u) == 0) {
         constexpr uint32_t NQ = EPB * OD / 4, IT = (NQ + NT - 1) / NT;
         const f4x* src4 = reinterpret_cast<const f4x*>(s_obs);
@@ -34,12 +53,12 @@ __device__ __forceinline__ void write_obs_rows(float* dst, const float* s_obs, u
 #pragma unroll
         for (uint32_t it = 0; it < IT; ++it) {
             const uint32_t k = tid + it * NT;
-            if (NQ % NT == 0 || k < NQ) __builtin_nontemporal_store(v[it], dst4 + k);
+            if (NQ % NT == 0 || k < NQ) obs_chunk_store<OBS_AUX>(dst4, r, k, v[it]);
         }
     } else {
         const f2x* src2 = reinterpret_cast<const f2x*>(s_obs);
         f2x* dst2 = reinterpret_cast<f2x*>(dst);
-        for (uint32_t k = tid; k < nvalid * od / 2; k += nthreads) __builtin_nontemporal_store(src2[k], dst2 + k);
+        for (uint32_t k = tid; k < nvalid * od / 2; k += nthreads) obs_chunk_store<OBS_AUX>(dst2, r, k, src2[k]);
     }
 }
 
@@ -140,10 +159,13 @@ __device__ __forceinline__ F4 f4(float x, float y, float z, float w) { return F4
 __device__ __forceinline__ float ib(int v) { return __int_as_float(v); }       // int field -> slot bits
 __device__ __forceinline__ int bi(float v) { return __float_as_int(v); }
 
-// ST_AUX: cache-policy bits of the state stores.  2 = nt: the step kernel's stores when the
-// working set exceeds the Infinity Cache (launch_step_t) -- at 1 Mi envs 185 -> 144 us, while at
+// ST_AUX: cache-policy bits of the state stores (AUX_*, cf2sim_internal.h; the context's policy
+// picks the kernel instance, DESIGN.md section 3 "Store cache policy").  AUX_NT: the step kernel's
+// stores when the working set exceeds the Infinity Cache -- at 1 Mi envs 185 -> 144 us, while at
 // 262 144 envs (cache-resident) nt stores cost +3 us, as nt loads do at both sizes (the loads
-// always use the default policy).
+// always use the default policy).  AUX_WT (sc1, write-through) where the working set is
+// cache-resident: the lines stay in the caches and the data goes out while the kernel runs, not in
+// the write-back of every dirty L2 line at the kernel's end (profiles/store_policy_ab.txt).
 template <int ST_AUX = 0>
 struct TileT {
     __amdgpu_buffer_rsrc_t r;

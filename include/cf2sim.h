@@ -203,6 +203,25 @@ int  cf2_last_hip_error(void);
 int  cf2_create(const cf2_config* cfg, cf2_ctx** out_ctx);
 int  cf2_destroy(cf2_ctx* ctx);
 int  cf2_layout_get(const cf2_ctx* ctx, cf2_layout* out);
+/* Cache policy of the stores of the large-N one-step kernel (cf2_step / cf2_step_packed above
+ * 32 768 envs per context; DESIGN.md section 3, "Store cache policy").  The fused kernels behind
+ * cf2_collect_step, cf2_collect_rollout and cf2_rollout have one form (plain state stores, nt
+ * observation rows) under every policy.  A policy is three values, each CF2_STORE_PLAIN (write-back), _NT (streamed past the Infinity
+ * Cache), _WT (write-through, sc1) or _NT_WT: out3[0] the state stores, out3[1] the observation
+ * rows, out3[2] the per-env outputs (rew, done, trunc, cost, level, final_obs).  cf2_create takes it
+ * from the environment variable CF2SIM_STORE_POLICY: "auto" (default: chosen from the env count and
+ * the bytes an env-step moves), "plain", "wt", "nt", or "state=P,obs=P,out=P" with P one of plain |
+ * wt | nt | nt_wt (parts left out keep the plain policy's value).  An unknown value makes cf2_create
+ * return CF2_ERR_INVALID_ARG, a policy the library has no kernel instance for CF2_ERR_UNSUPPORTED.
+ * Contexts of up to 32 768 envs run kernels with one fixed policy and report that one.
+ * cf2_store_policy: what ctx's cf2_step runs.  cf2_store_policy_for: what cf2_create would pick for cfg under
+ * `text` (NULL: the environment variable), without touching a device.  Results never depend on it. */
+#define CF2_STORE_PLAIN 0
+#define CF2_STORE_NT    2
+#define CF2_STORE_WT    16
+#define CF2_STORE_NT_WT 18
+int  cf2_store_policy(const cf2_ctx* ctx, uint32_t* out3);
+int  cf2_store_policy_for(const cf2_config* cfg, const char* text, uint32_t* out3);
 
 /* Bind HJ value tables: V_dev = [num_tables][15^6] float32 C-order [roll,pitch,yaw,p,q,r]
  * (the on-disk fastrack_{level}_15x15.npy format).  table_level_index maps Boltzmann level
