@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = (
     "cf2_rollout", "cf2_get_state", "cf2_set_state", "cf2_hj_disturbance",
     "cf2_policy_weights_count", "cf2_policy_packed_count", "cf2_policy_pack", "cf2_policy_forward", "cf2_value_forward_masked", "cf2_gae",
     "cf2_episode_stats_scratch_bytes", "cf2_episode_stats", "cf2_column_moments_scratch_bytes", "cf2_column_moments",
-    "cf2_ppo_scratch_bytes", "cf2_ppo_policy_grad", "cf2_ppo_value_grad",
+    "cf2_ppo_scratch_bytes", "cf2_ppo_policy_grad", "cf2_ppo_value_grad", "cf2_ppo_policy_grad_gated", "cf2_adam_step",
     "cf2_hbm_probe", "cf2_step_packed", "cf2_obs_packed_words", "cf2_xchg_send_words", "cf2_obs_pack", "cf2_obs_consume", "cf2_obs_rows",
     "cf2_xchg_bind", "cf2_xchg_unique_id", "cf2_xchg_create", "cf2_xchg_destroy", "cf2_xchg_register",
     "cf2_xchg_publish", "cf2_xchg_wait_free", "cf2_xchg_wait", "cf2_xchg_pred_to_host", "cf2_xchg_begin", "cf2_xchg_step", "cf2_xchg_end", "cf2_xchg_env_step", "cf2_xchg_run",
@@ -112,6 +112,8 @@ def load() -> ctypes.CDLL:
     lib.cf2_ppo_scratch_bytes.argtypes = [u32, u32]
     lib.cf2_ppo_policy_grad.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, u32, vp, ctypes.c_float] + [vp] * 7
     lib.cf2_ppo_value_grad.argtypes = [vp, u32, vp, vp, u32, vp, u32] + [vp] * 5
+    lib.cf2_ppo_policy_grad_gated.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, u32, vp, ctypes.c_float] + [vp] * 8
+    lib.cf2_adam_step.argtypes = [vp, vp, vp, vp, u32, u32, vp] + [ctypes.c_float] * 5 + [vp, vp, ctypes.c_float, vp, vp]
     lib.cf2_hbm_probe.argtypes =[vp, vp, ctypes.c_size_t, ctypes.c_int, vp]
     lib.cf2_obs_packed_words.restype = ctypes.c_size_t
     lib.cf2_obs_packed_words.argtypes = [u32, u32, u32]

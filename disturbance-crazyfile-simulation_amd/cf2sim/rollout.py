@@ -270,6 +270,28 @@ def pack_policy_weights(ac: MLPActorCritic) -> torch.Tensor:
     return torch.cat([p.float().reshape(-1) for p in parts]).contiguous()
 
 
+@torch.no_grad()
+def unpack_policy_weights(ac: MLPActorCritic, flat: torch.Tensor) -> None:
+    """The inverse of ``pack_policy_weights`` for the twelve Linear tensors (pi W1 b1 W2 b2 W3 b3,
+    v likewise): copy them out of a flat block into the module, bit for bit.  ``log_std`` and the
+    observation statistics are left alone (the module owns them; the block only carries copies)."""
+    lin_pi = [m for m in ac.pi_net if isinstance(m, nn.Linear)]
+    lin_v = [m for m in ac.v_net if isinstance(m, nn.Linear)]
+    d = lin_pi[0].in_features
+    want = sum(m.weight.numel() + m.bias.numel() for m in lin_pi + lin_v) + ac.log_std.numel() + 2 * d
+    if flat.dim() != 1 or flat.numel() != want or flat.dtype != torch.float32:
+        raise ValueError(f"flat must be a float32 block of {want} words, got {tuple(flat.shape)} {flat.dtype}")
+    off = 0
+    for lins in (lin_pi, lin_v):
+        for m in lins:
+            nw, nb = m.weight.numel(), m.bias.numel()
+            m.weight.copy_(flat[off:off + nw].view(m.in_features, m.out_features).t())
+            m.bias.copy_(flat[off + nw:off + nw + nb])
+            off += nw + nb
+        if lins is lin_pi:
+            off += ac.log_std.numel()
+
+
 POLICY_PRECISIONS = {"fp32": 0, "bf16x3": 1}     # cf2_policy_precision (include/cf2sim.h)
 
 
@@ -299,10 +321,18 @@ class FusedActorCritic:
     def sync(self):
         """Re-pack the weights: the flat block (pack_policy_weights) -> the kernel's MFMA fragment
         block (cf2_policy_pack, one launch)."""
+        dev = next(self.ac.parameters()).device
+        self.sync_from_flat(pack_policy_weights(self.ac).to(dev))
+
+    def sync_from_flat(self, flat: torch.Tensor):
+        """``sync()`` straight from a flat block (the layout of pack_policy_weights) that already
+        holds the module's values, e.g. the one a device-side optimiser stepped."""
         from . import _native
         dev = next(self.ac.parameters()).device
-        flat = pack_policy_weights(self.ac).to(dev)
-        assert flat.numel() == self.lib.cf2_policy_weights_count(self.obs_dim)
+        if not isinstance(flat, torch.Tensor) or flat.dtype != torch.float32 or flat.device != dev \
+                or not flat.is_contiguous() or flat.numel() != self.lib.cf2_policy_weights_count(self.obs_dim):
+            raise ValueError(f"flat must be a contiguous float32 block of "
+                             f"{self.lib.cf2_policy_weights_count(self.obs_dim)} words on {dev}")
         self.w = torch.empty(self.lib.cf2_policy_packed_count(self.obs_dim, self.prec), device=dev)
         self.w_ptr = self.w.data_ptr()
         _native.check(self.lib.cf2_policy_pack(flat.data_ptr(), self.obs_dim, self.prec, self.w.data_ptr(),
@@ -673,5 +703,5 @@ def collect(envs, ac, steps: int, obs: torch.Tensor | None = None, gamma: float 
     return Rollout(buf_o, buf_a, buf_r, buf_v, buf_lp, buf_d, buf_tr, adv, ret, o, last_val, trunc_val, disc)
 
 
-__all__ = ["OnlineMeanStd", "MLPActorCritic", "FusedActorCritic", "pack_policy_weights", "gae", "gae_device", "collect",
+__all__ = ["OnlineMeanStd", "MLPActorCritic", "FusedActorCritic", "pack_policy_weights", "unpack_policy_weights", "gae", "gae_device", "collect",
            "Rollout", "update_running_statistics", "EpisodeStats"]

@@ -80,6 +80,7 @@ struct PpoArgs {
     float* part_grad;            // [blocks][NPAR]
     uint32_t n, m;
     float clip;
+    const uint32_t* gate;        // optional: a non-zero word makes the launch return at once, nothing written
 };
 
 // LDS written by some lanes of the wave and read by others: DS instructions of one wave execute in
@@ -114,6 +115,7 @@ __global__ void __launch_bounds__(PPO_BLOCK) ppo_kernel(const PpoArgs a) {
     using N = PpoNet<D, PI>;
     using L = PolicyLayout<D>;
     constexpr int H = N::H, NO = N::NO, WS = PPO_WS, AS = PPO_AS, ZS = PPO_ZS;
+    if (a.gate && *a.gate != 0u) return;          // the same word for every block: this launch only reads it
     __shared__ __attribute__((aligned(16))) float lds[N::LDS_FLOATS];
     __shared__ double sred[PPO_WAVES][PPO_SUM];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
@@ -511,11 +513,13 @@ __global__ void __launch_bounds__(PPO_BLOCK) ppo_kernel(const PpoArgs a) {
 }
 
 // Block partials -> gradient slice and summary: fp64 sums in block-index order, divided by m, one
-// rounding to fp32.  grad == nullptr: the summary only.
+// rounding to fp32.  grad == nullptr: the summary only.  gate: as PpoArgs::gate.
 __global__ void __launch_bounds__(256) ppo_merge_kernel(const float* __restrict__ part_grad,
                                                         const double* __restrict__ part_sum, uint32_t blocks,
                                                         uint32_t npar, uint32_t m, float* __restrict__ grad,
-                                                        double* __restrict__ summary) {
+                                                        double* __restrict__ summary,
+                                                        const uint32_t* __restrict__ gate) {
+    if (gate && *gate != 0u) return;
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (grad && p < npar) {
         double acc = 0.0;
@@ -551,7 +555,7 @@ static int ppo_launch(PpoArgs a, float* grad, double* summary, void* scratch, hi
     if (e != hipSuccess) return hip_fail(e);
     const uint32_t mblocks = grad ? (N::NPAR + 255u) / 256u : 1u;
     hipLaunchKernelGGL(ppo_merge_kernel, dim3(mblocks), dim3(256), 0, s, a.part_grad, a.part_sum, blocks,
-                       (uint32_t)N::NPAR, a.m, grad ? grad + N::BASE : nullptr, summary);
+                       (uint32_t)N::NPAR, a.m, grad ? grad + N::BASE : nullptr, summary, a.gate);
     e = hipGetLastError();
     return e == hipSuccess ? CF2_OK : hip_fail(e);
 }
@@ -567,11 +571,11 @@ extern "C" size_t cf2_ppo_scratch_bytes(uint32_t m, uint32_t obs_dim) {
     return (size_t)PPO_MAX_BLOCKS * PPO_SUM * sizeof(double) + (size_t)ppo_blocks(m) * ppo_npar_max(obs_dim) * sizeof(float);
 }
 
-extern "C" int cf2_ppo_policy_grad(const float* weights_dev, uint32_t obs_dim, const float* obs_dev, const float* act_dev,
-                                   const float* logp_old_dev, const float* adv_dev, uint32_t n, const uint32_t* idx_dev,
-                                   uint32_t m, const double* adv_moments_dev, float clip_ratio, const float* mu_old_dev,
-                                   float* mu_out_dev, float* logp_out_dev, float* grad_dev, double* summary_dev,
-                                   void* scratch_dev, void* stream) {
+static int policy_grad(const float* weights_dev, uint32_t obs_dim, const float* obs_dev, const float* act_dev,
+                       const float* logp_old_dev, const float* adv_dev, uint32_t n, const uint32_t* idx_dev, uint32_t m,
+                       const double* adv_moments_dev, float clip_ratio, const float* mu_old_dev, float* mu_out_dev,
+                       float* logp_out_dev, float* grad_dev, double* summary_dev, void* scratch_dev,
+                       const uint32_t* ctrl_dev, void* stream) {
     if (obs_dim != 34 && obs_dim != 42) return CF2_ERR_UNSUPPORTED;
     if (m == 0) return CF2_OK;
     if (!weights_dev || !obs_dev || !act_dev || !logp_old_dev || !adv_dev || !summary_dev || !scratch_dev || n == 0 ||
@@ -580,13 +584,34 @@ extern "C" int cf2_ppo_policy_grad(const float* weights_dev, uint32_t obs_dim, c
     if (misaligned(weights_dev, 4) || misaligned(obs_dev, 8) || misaligned(act_dev, 16) || misaligned(logp_old_dev, 4) ||
         misaligned(adv_dev, 4) || misaligned(idx_dev, 4) || misaligned(adv_moments_dev, 8) || misaligned(mu_old_dev, 4) ||
         misaligned(mu_out_dev, 4) || misaligned(logp_out_dev, 4) || misaligned(grad_dev, 4) || misaligned(summary_dev, 8) ||
-        misaligned(scratch_dev, 8))
+        misaligned(scratch_dev, 8) || misaligned(ctrl_dev, 4))
         return CF2_ERR_INVALID_ARG;
     PpoArgs a = {weights_dev, obs_dev, act_dev, logp_old_dev, adv_dev, idx_dev, adv_moments_dev, mu_old_dev, mu_out_dev,
-                 logp_out_dev, nullptr, nullptr, n, m, clip_ratio};
+                 logp_out_dev, nullptr, nullptr, n, m, clip_ratio, ctrl_dev};
     const hipStream_t s = (hipStream_t)stream;
     return obs_dim == 34 ? ppo_launch<34, true>(a, grad_dev, summary_dev, scratch_dev, s)
                          : ppo_launch<42, true>(a, grad_dev, summary_dev, scratch_dev, s);
+}
+
+extern "C" int cf2_ppo_policy_grad(const float* weights_dev, uint32_t obs_dim, const float* obs_dev, const float* act_dev,
+                                   const float* logp_old_dev, const float* adv_dev, uint32_t n, const uint32_t* idx_dev,
+                                   uint32_t m, const double* adv_moments_dev, float clip_ratio, const float* mu_old_dev,
+                                   float* mu_out_dev, float* logp_out_dev, float* grad_dev, double* summary_dev,
+                                   void* scratch_dev, void* stream) {
+    return policy_grad(weights_dev, obs_dim, obs_dev, act_dev, logp_old_dev, adv_dev, n, idx_dev, m, adv_moments_dev,
+                       clip_ratio, mu_old_dev, mu_out_dev, logp_out_dev, grad_dev, summary_dev, scratch_dev, nullptr,
+                       stream);
+}
+
+extern "C" int cf2_ppo_policy_grad_gated(const float* weights_dev, uint32_t obs_dim, const float* obs_dev,
+                                         const float* act_dev, const float* logp_old_dev, const float* adv_dev, uint32_t n,
+                                         const uint32_t* idx_dev, uint32_t m, const double* adv_moments_dev,
+                                         float clip_ratio, const float* mu_old_dev, float* mu_out_dev, float* logp_out_dev,
+                                         float* grad_dev, double* summary_dev, void* scratch_dev,
+                                         const uint32_t* ctrl_dev, void* stream) {
+    return policy_grad(weights_dev, obs_dim, obs_dev, act_dev, logp_old_dev, adv_dev, n, idx_dev, m, adv_moments_dev,
+                       clip_ratio, mu_old_dev, mu_out_dev, logp_out_dev, grad_dev, summary_dev, scratch_dev, ctrl_dev,
+                       stream);
 }
 
 extern "C" int cf2_ppo_value_grad(const float* weights_dev, uint32_t obs_dim, const float* obs_dev, const float* target_dev,
@@ -600,7 +625,7 @@ extern "C" int cf2_ppo_value_grad(const float* weights_dev, uint32_t obs_dim, co
         misaligned(val_out_dev, 4) || misaligned(grad_dev, 4) || misaligned(summary_dev, 8) || misaligned(scratch_dev, 8))
         return CF2_ERR_INVALID_ARG;
     PpoArgs a = {weights_dev, obs_dev, nullptr, nullptr, target_dev, idx_dev, nullptr, nullptr, nullptr, val_out_dev,
-                 nullptr, nullptr, n, m, 0.0f};
+                 nullptr, nullptr, n, m, 0.0f, nullptr};
     const hipStream_t s = (hipStream_t)stream;
     return obs_dim == 34 ? ppo_launch<34, false>(a, grad_dev, summary_dev, scratch_dev, s)
                          : ppo_launch<42, false>(a, grad_dev, summary_dev, scratch_dev, s);

@@ -430,6 +430,49 @@ int  cf2_ppo_value_grad(const float* weights_dev, uint32_t obs_dim, const float*
                         uint32_t n, const uint32_t* idx_dev, uint32_t m, float* val_out_dev, float* grad_dev,
                         double* summary_dev, void* scratch_dev, void* stream);
 
+/* cf2_ppo_policy_grad behind a gate, for an update loop that never returns to the host: ctrl_dev is
+ * the control block of cf2_adam_step (below).  NULL, or ctrl_dev[0] == 0 when the kernels start:
+ * exactly cf2_ppo_policy_grad, the same bits in every output.  ctrl_dev[0] != 0: both launches return
+ * at once; grad, summary, mu_out, logp_out and the scratch are left untouched.  The launches only read
+ * the word.  Errors as cf2_ppo_policy_grad; ctrl_dev is 4-byte aligned. */
+int  cf2_ppo_policy_grad_gated(const float* weights_dev, uint32_t obs_dim, const float* obs_dev, const float* act_dev,
+                               const float* logp_old_dev, const float* adv_dev, uint32_t n, const uint32_t* idx_dev,
+                               uint32_t m, const double* adv_moments_dev, float clip_ratio, const float* mu_old_dev,
+                               float* mu_out_dev, float* logp_out_dev, float* grad_dev, double* summary_dev,
+                               void* scratch_dev, const uint32_t* ctrl_dev, void* stream);
+
+/* One optimiser step on a slice of the flat weight block, one launch: torch.optim.Adam with its
+ * defaults (no amsgrad, no weight decay) preceded by torch.nn.utils.clip_grad_norm_ (the reference
+ * clips the actor's and the critic's gradients before the optimiser step), and the stop rule of
+ * update_policy_net (algs/iwpg/iwpg.py: `if kl > target_kl: break`) applied on the device.
+ * weights, grad, exp_avg and exp_avg_sq are whole flat blocks in the layout of cf2_policy_pack's
+ * input; the call reads the words [begin, begin + count) of grad, reads and writes the same words of
+ * the other three and touches nothing else.  step_dev: one uint32, the optimiser's step count (on
+ * the device, so that a skipped call does not advance it).  ctrl_dev (optional): four uint32, zeroed
+ * by the caller when an update starts: [0] stop flag, [1] steps applied under this block, [2..3]
+ * reserved, left 0.
+ *   1. ctrl_dev[0] != 0: return, nothing is written.
+ *   2. ctrl_dev and kl_summary_dev given and kl_summary_dev[4] (the mean exact KL of a policy
+ *      summary) > (double)target_kl: ctrl_dev[0] = 1, nothing else is written.  The comparison is
+ *      strict and false for a NaN, as the reference's.
+ *   3. otherwise t = ++*step_dev; norm = sqrt(sum g^2) over the slice; with max_grad_norm > 0
+ *      g = g min(1, max_grad_norm / (norm + 1e-6)) (grad_dev itself is never written);
+ *      m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g^2;
+ *      w = w - lr / (1 - beta1^t) m / (sqrt(v) / sqrt(1 - beta2^t) + eps); ++ctrl_dev[1];
+ *      *norm_out_dev (optional) = norm, the norm before clipping that torch's function returns.
+ * The hyper-parameters are the fp32 values passed (0.999f, not 0.999).  The norm, the bias
+ * corrections and every word's update are evaluated in fp64 and rounded once into the fp32 state;
+ * non-finite gradients get no special case.  One workgroup, no atomics, sums in a fixed order: the
+ * same input gives the same bits, and nothing but this launch writes the stop flag.
+ * count == 0: CF2_OK, nothing launched; a NULL weights, grad, exp_avg, exp_avg_sq or step pointer, a
+ * misaligned pointer (4 bytes; 8 for norm_out and kl_summary), begin + count past 32 bits, lr
+ * negative or not finite: CF2_ERR_INVALID_ARG; count > 2^20: CF2_ERR_UNSUPPORTED.  Every error
+ * returns before anything is launched. */
+int  cf2_adam_step(float* weights_dev, const float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev,
+                   uint32_t begin, uint32_t count, uint32_t* step_dev, float lr, float beta1, float beta2, float eps,
+                   float max_grad_norm, double* norm_out_dev, const double* kl_summary_dev, float target_kl,
+                   uint32_t* ctrl_dev, void* stream);
+
 /* Multi-GPU observation exchange as deltas (the north star's per-step RCCL
  * all-gather of the obs slab).  The reference has no counterpart: its MPI ranks exchange only
  * gradients and statistics (utils/mpi_tools.py:30-44); the rows materialised here are exactly what
