@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = (
     "cf2_policy_weights_count", "cf2_policy_packed_count", "cf2_policy_pack", "cf2_policy_forward", "cf2_value_forward_masked", "cf2_gae",
     "cf2_episode_stats_scratch_bytes", "cf2_episode_stats", "cf2_column_moments_scratch_bytes", "cf2_column_moments",
     "cf2_ppo_scratch_bytes", "cf2_ppo_policy_grad", "cf2_ppo_value_grad", "cf2_ppo_policy_grad_gated", "cf2_adam_step",
+    "cf2_ppo_fisher_vec", "cf2_ng_cg_init", "cf2_ng_cg_step", "cf2_ng_direction", "cf2_ng_line_search",
     "cf2_hbm_probe", "cf2_step_packed", "cf2_obs_packed_words", "cf2_xchg_send_words", "cf2_obs_pack", "cf2_obs_consume", "cf2_obs_rows",
     "cf2_xchg_bind", "cf2_xchg_unique_id", "cf2_xchg_create", "cf2_xchg_destroy", "cf2_xchg_register",
     "cf2_xchg_publish", "cf2_xchg_wait_free", "cf2_xchg_wait", "cf2_xchg_pred_to_host", "cf2_xchg_begin", "cf2_xchg_step", "cf2_xchg_end", "cf2_xchg_env_step", "cf2_xchg_run",
@@ -114,6 +115,11 @@ def load() -> ctypes.CDLL:
     lib.cf2_ppo_value_grad.argtypes = [vp, u32, vp, vp, u32, vp, u32] + [vp] * 5
     lib.cf2_ppo_policy_grad_gated.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, u32, vp, ctypes.c_float] + [vp] * 8
     lib.cf2_adam_step.argtypes = [vp, vp, vp, vp, u32, u32, vp] + [ctypes.c_float] * 5 + [vp, vp, ctypes.c_float, vp, vp]
+    lib.cf2_ppo_fisher_vec.argtypes = [vp, u32, vp, u32, vp, u32] + [vp] * 6
+    lib.cf2_ng_cg_init.argtypes = [vp] * 5 + [u32, u32, vp, vp, vp]
+    lib.cf2_ng_cg_step.argtypes = [vp] * 4 + [u32, u32, ctypes.c_float, vp, vp, vp]
+    lib.cf2_ng_direction.argtypes = [vp] * 6 + [u32, u32, ctypes.c_float, ctypes.c_float, vp, vp, vp]
+    lib.cf2_ng_line_search.argtypes = [vp] * 3 + [u32] * 4 + [ctypes.c_float, ctypes.c_float] + [vp] * 5
     lib.cf2_hbm_probe.argtypes =[vp, vp, ctypes.c_size_t, ctypes.c_int, vp]
     lib.cf2_obs_packed_words.restype = ctypes.c_size_t
     lib.cf2_obs_packed_words.argtypes = [u32, u32, u32]

@@ -11,7 +11,7 @@ SRC_DIR = os.path.abspath(os.path.join(PKG_DIR, "..", "csrc"))
 INC_DIR = os.path.abspath(os.path.join(PKG_DIR, "..", "..", "include"))
 LIB = os.path.join(PKG_DIR, "libcf2sim.so")
 SOURCES = ["cf2sim_kernels.hip", "cf2sim_policy.hip", "cf2sim_util.hip", "cf2sim_exchange.hip", "cf2sim_stats.hip",
-           "cf2sim_ppo.hip", "cf2sim_optim.hip", "cf2sim_api.cpp"]
+           "cf2sim_ppo.hip", "cf2sim_optim.hip", "cf2sim_natgrad.hip", "cf2sim_api.cpp"]
 # every header of csrc/ is part of every object's content key: one left out would let a stale
 # library pass for up to date
 HEADERS = sorted(f for f in os.listdir(SRC_DIR) if f.endswith(".h"))
@@ -35,14 +35,16 @@ SOURCE_FLAGS = {"cf2sim_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=on"]
                 "cf2sim_policy.hip": ["-fno-slp-vectorize", "-ffp-contract=on"],
                 "cf2sim_stats.hip": ["-ffp-contract=off"],
                 "cf2sim_ppo.hip": ["-fno-slp-vectorize", "-ffp-contract=on"],
-                "cf2sim_optim.hip": ["-ffp-contract=off"]}
+                "cf2sim_optim.hip": ["-ffp-contract=off"],
+                "cf2sim_natgrad.hip": ["-ffp-contract=off"]}
 # The policy TU contracts like the env kernels too: the fused collect kernel (cf2sim_kernels.hip)
 # runs the same policy code (cf2sim_policy.h), and with "fast" the policy kernel alone fused the
 # standardisation's product into the hi/lo split's subtraction (8 v_fma instead of v_sub), so the
 # two paths' actions and values differed in the last bit in ~20 % of rows.
 # The statistics TU contracts nothing implicitly: its episode sums are compared bit for bit with
 # plain f32 adds; the fp64 moment sums call fma() where they mean one.
-# The optimiser TU likewise: the Adam update is the formula as written, in fp64, rounded once.
+# The optimiser TU likewise: the Adam update is the formula as written, in fp64, rounded once; and the
+# natural-gradient solver TU (conjugate gradients, step size, line search) for the same reason.
 
 
 def _hipcc() -> str:

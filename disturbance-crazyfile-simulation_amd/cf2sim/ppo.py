@@ -4,7 +4,9 @@
 both networks from the fused HIP kernels of csrc/cf2sim_ppo.hip (cf2_ppo_policy_grad,
 cf2_ppo_value_grad) and a torch optimiser on the module's parameters (``PPOUpdater``), or with the
 optimiser and the KL stop on the device too (``ResidentPPOUpdater``: cf2_adam_step of
-csrc/cf2sim_optim.hip on the flat weight block, cf2_ppo_policy_grad_gated).
+csrc/cf2sim_optim.hip on the flat weight block, cf2_ppo_policy_grad_gated).  The second half of the
+module is the reference's TRPO and NPG updates (``NaturalGradientUpdater``: cf2_ppo_fisher_vec and the
+solver kernels of csrc/cf2sim_natgrad.hip); its header comment restates their rules.
 
 Reference behaviour restated (paths relative to phoenix_drone_simulation/algs/):
 
@@ -502,6 +504,431 @@ class ResidentPPOUpdater:
         return self.result() if read else None
 
 
+# ---------------------------------------------------------------------------------------------------
+# Natural-gradient updates (the reference's algs/npg and algs/trpo)
+#
+# * ``algs/npg``: g = gradient of the unclipped surrogate -mean(ratio A); x = conjugate gradients
+#   (``cg_iters`` steps) on (F + damping I) x = -g, where F v is the Hessian-vector product of the mean
+#   KL to the detached policy on every ``fvp_stride``-th row; alpha = sqrt(2 target_kl / (x.Hx + 1e-8));
+#   step = alpha x; the parameters move by the full step.
+# * ``algs/trpo``: the same direction, then a backtracking line search over step fractions
+#   decay^j, j = 0 .. line_search_steps - 1: the first trial with a finite loss, an improvement
+#   loss_before - loss >= 0 and KL <= 1.5 target_kl is kept; with none the old parameters come back.
+# * The critic is IWPG's ``update_value_net``, as in the PPO update.
+#
+# For this policy (Gaussian, log_std not trained) KL = sum_k (mu_old_k - mu_k)^2 / (2 sigma_k^2), whose
+# Hessian at mu = mu_old is exactly F = (1/m) sum_rows J^T Sigma^-1 J: cf2_ppo_fisher_vec evaluates
+# that with one tangent pass and the gradient kernel's backward pass; ``fisher_vec_torch`` is the
+# reference's double-backward form.  Vectors are in the flat layout of ``pack_policy_weights``
+# (matrices input-major), the policy slice [0, flat_slice(ac, "pi")[1]).
+# ---------------------------------------------------------------------------------------------------
+NG_STATE_DOUBLES = 16
+# include/cf2sim.h CF2_NG_*: the words of ng_state
+(NG_RDOTR, NG_CG_STEPS, NG_CG_DONE, NG_XHX, NG_ALPHA, NG_EXPECTED, NG_STEP_FRAC, NG_ACCEPT_STEP, NG_LOSS_BEFORE,
+ NG_LOSS_AFTER, NG_KL_AFTER, NG_PDOTZ, NG_BDOTB, NG_RESIDUAL) = range(14)
+
+
+def pi_flat(ac: MLPActorCritic, tensors=None) -> torch.Tensor:
+    """The policy slice of the flat layout from six tensors shaped like ac.pi_net's parameters
+    (W1 b1 W2 b2 W3 b3; default: the parameters themselves, detached)."""
+    params = [p for m in _linears(ac, "pi") for p in (m.weight, m.bias)]
+    tensors = [p.detach() for p in params] if tensors is None else list(tensors)
+    return torch.cat([t.t().reshape(-1) if t.dim() == 2 else t.reshape(-1) for t in tensors])
+
+
+def pi_unflat(ac: MLPActorCritic, vec: torch.Tensor) -> list:
+    """The inverse of ``pi_flat``: views of the first words of ``vec`` shaped like the parameters."""
+    out, off = [], 0
+    for m in _linears(ac, "pi"):
+        nw, nb = m.weight.numel(), m.bias.numel()
+        out += [vec[off:off + nw].view(m.in_features, m.out_features).t(), vec[off + nw:off + nw + nb]]
+        off += nw + nb
+    return out
+
+
+@torch.no_grad()
+def set_pi_flat(ac: MLPActorCritic, vec: torch.Tensor) -> None:
+    """Copy a flat policy slice into ac.pi_net's parameters."""
+    params = [p for m in _linears(ac, "pi") for p in (m.weight, m.bias)]
+    for p, src in zip(params, pi_unflat(ac, vec)):
+        p.copy_(src)
+
+
+def fisher_vec_torch(ac: MLPActorCritic, obs, vec) -> torch.Tensor:
+    """F vec in the reference's form: the gradient of (grad KL . vec), KL the mean divergence to the
+    detached policy on the rows ``obs``, through autograd twice.  vec: a flat policy slice (or a
+    longer block whose first words are one); any dtype and device.  Returns the flat policy slice."""
+    params = [p for m in _linears(ac, "pi") for p in (m.weight, m.bias)]
+    with torch.enable_grad():
+        mu = ac.pi_net(_standardized(ac, obs))
+        log_std = ac.log_std.detach().to(mu.dtype)
+        kl = ((mu.detach() - mu) ** 2 * (0.5 * torch.exp(-2.0 * log_std))).sum(-1).mean()
+        grads = torch.autograd.grad(kl, params, create_graph=True)
+        gv = sum((g * v.to(g.dtype)).sum() for g, v in zip(grads, pi_unflat(ac, vec.detach())))
+        hv = torch.autograd.grad(gv, params)
+    return pi_flat(ac, [h.detach() for h in hv])
+
+
+def cg_init_torch(grad: torch.Tensor) -> dict:
+    """cf2_ng_cg_init restated: b = -grad, x = 0, r = p = b, rdotr = b.b.  The state is a dict of
+    tensors of grad's dtype (scalars 0-dim) plus the Python values ``done`` and ``steps``."""
+    b = -grad.detach()
+    bb = torch.dot(b, b)
+    return {"b": b, "x": torch.zeros_like(b), "r": b.clone(), "p": b.clone(), "rdotr": bb, "bdotb": bb, "residual": bb,
+            "done": False, "steps": 0}
+
+
+def cg_step_torch(st: dict, z: torch.Tensor, damping: float) -> None:
+    """cf2_ng_cg_step restated, given z = F p."""
+    if st["done"]:
+        return
+    zd = z + damping * st["p"]
+    alpha = st["rdotr"] / (torch.dot(st["p"], zd) + 1e-6)
+    st["x"] = st["x"] + alpha * st["p"]
+    st["r"] = st["r"] - alpha * zd
+    new = torch.dot(st["r"], st["r"])
+    st["steps"] += 1
+    st["residual"] = new
+    if float(torch.sqrt(new)) < 1e-10:
+        st["done"] = True
+        return
+    st["p"] = st["r"] + new / (st["rdotr"] + 1e-6) * st["p"]
+    st["rdotr"] = new
+
+
+def direction_torch(st: dict, z: torch.Tensor, damping: float, target_kl: float) -> None:
+    """cf2_ng_direction restated, given z = F x: xHx, alpha, step and the expected improvement."""
+    x = st["x"]
+    st["xHx"] = torch.dot(x, z + damping * x)
+    st["alpha"] = torch.sqrt(2.0 * target_kl / (st["xHx"] + 1e-8))
+    st["step"] = st["alpha"] * x
+    st["expected"] = torch.dot(st["b"], st["step"])
+
+
+def line_search_torch(trial: int, total: int, decay: float, target_kl: float, loss: float, kl: float,
+                      loss_before: float) -> tuple:
+    """cf2_ng_line_search's decision restated: ("accept", decay^trial), ("retry", decay^(trial + 1))
+    or ("restore", 0.0) after the last trial."""
+    import math
+    if math.isfinite(loss) and loss_before - loss >= 0.0 and kl <= 1.5 * target_kl:
+        return "accept", decay ** trial
+    if trial + 1 < total:
+        return "retry", decay ** (trial + 1)
+    return "restore", 0.0
+
+
+def fisher_vec_device(flat, obs, vec, out, summary, scratch, idx=None, m: int | None = None, ctrl=None):
+    """cf2_ppo_fisher_vec on torch buffers (include/cf2sim.h describes every argument): the policy
+    slice of ``out`` = F vec on the rows ``idx`` (default: the first m) of ``obs``, no damping.  vec and
+    out are float32 blocks as long as ``flat``; summary[1] = vec^T F vec.  Nothing synchronises."""
+    from . import _native
+    from .vec_env import _check_buf
+    lib = _native.load()
+    n = obs.shape[0]
+    m = int(m) if m is not None else (idx.shape[0] if idx is not None else n)
+    if vec is None or out is None:
+        raise ValueError("vec and out are required")
+    d, dev = _check_common(lib, flat, obs, n, idx, m, out, summary, scratch)
+    _check_buf(vec, "vec", (flat.numel(),), torch.float32, dev)
+    _check_buf(ctrl, "ctrl", (4,), torch.int32, dev)
+    p = _native.ptr
+    _native.check(lib.cf2_ppo_fisher_vec(p(flat), d, p(obs), n, p(idx), m, p(vec), p(out), p(summary), p(scratch), p(ctrl),
+                                         torch.cuda.current_stream(dev).cuda_stream), "cf2_ppo_fisher_vec")
+    return summary
+
+
+def _check_ng(blocks: dict, begin: int, count: int, ng_state, ctrl, ctrl_required=False):
+    from .vec_env import _check_buf
+    first = next(iter(blocks.values()))
+    if not isinstance(first, torch.Tensor) or first.dim() != 1 or first.device.type != "cuda":
+        raise ValueError("the solver kernels need 1-d blocks on the GPU")
+    dev, words = first.device, first.numel()
+    begin, count = int(begin), int(count)
+    if begin < 0 or count < 0 or begin + count > words:
+        raise ValueError(f"the slice [{begin}, {begin + count}) does not lie in a block of {words} words")
+    for name, t in blocks.items():
+        if t is None:
+            raise ValueError(f"{name} is required")
+        _check_buf(t, name, (words,), torch.float32, dev)
+    if ng_state is None:
+        raise ValueError("ng_state is required")
+    _check_buf(ng_state, "ng_state", (NG_STATE_DOUBLES,), torch.float64, dev, align=8)
+    if ctrl is None and ctrl_required:
+        raise ValueError("ctrl is required")
+    _check_buf(ctrl, "ctrl", (4,), torch.int32, dev)
+    return begin, count, torch.cuda.current_stream(dev).cuda_stream
+
+
+def ng_cg_init_device(grad, b, x, r, p, begin: int, count: int, ng_state, ctrl=None) -> None:
+    """cf2_ng_cg_init on torch buffers: float32 blocks of one length, ng_state float64 [16]."""
+    from . import _native
+    begin, count, stream = _check_ng({"grad": grad, "b": b, "x": x, "r": r, "p": p}, begin, count, ng_state, ctrl)
+    q = _native.ptr
+    _native.check(_native.load().cf2_ng_cg_init(q(grad), q(b), q(x), q(r), q(p), begin, count, q(ng_state), q(ctrl), stream),
+                  "cf2_ng_cg_init")
+
+
+def ng_cg_step_device(z, x, r, p, begin: int, count: int, damping: float, ng_state, ctrl=None) -> None:
+    """cf2_ng_cg_step on torch buffers, given z = F p."""
+    from . import _native
+    begin, count, stream = _check_ng({"z": z, "x": x, "r": r, "p": p}, begin, count, ng_state, ctrl)
+    q = _native.ptr
+    _native.check(_native.load().cf2_ng_cg_step(q(z), q(x), q(r), q(p), begin, count, float(damping), q(ng_state), q(ctrl),
+                                                stream), "cf2_ng_cg_step")
+
+
+def ng_direction_device(z, x, b, step, flat, flat_old, begin: int, count: int, damping: float, target_kl: float,
+                        ng_state, ctrl=None) -> None:
+    """cf2_ng_direction on torch buffers, given z = F x: writes step, flat_old = flat, flat += step."""
+    from . import _native
+    begin, count, stream = _check_ng({"z": z, "x": x, "b": b, "step": step, "flat": flat, "flat_old": flat_old}, begin,
+                                     count, ng_state, ctrl)
+    q = _native.ptr
+    _native.check(_native.load().cf2_ng_direction(q(z), q(x), q(b), q(step), q(flat), q(flat_old), begin, count,
+                                                  float(damping), float(target_kl), q(ng_state), q(ctrl), stream),
+                  "cf2_ng_direction")
+
+
+def ng_line_search_device(flat, flat_old, step, begin: int, count: int, trial: int, total: int, decay: float,
+                          target_kl: float, eval_summary, loss_before, ng_state, ctrl) -> None:
+    """cf2_ng_line_search on torch buffers: eval_summary float64 [8] (the gated evaluation of trial
+    ``trial``), loss_before float64 [1] (e.g. ``summary0[1:2]``), ctrl int32 [4]."""
+    from . import _native
+    from .vec_env import _check_buf
+    begin, count, stream = _check_ng({"flat": flat, "flat_old": flat_old, "step": step}, begin, count, ng_state, ctrl,
+                                     ctrl_required=True)
+    if eval_summary is None or loss_before is None:
+        raise ValueError("eval_summary and loss_before are required")
+    _check_buf(eval_summary, "eval_summary", (8,), torch.float64, flat.device, align=8)
+    _check_buf(loss_before, "loss_before", (1,), torch.float64, flat.device, align=8)
+    q = _native.ptr
+    _native.check(_native.load().cf2_ng_line_search(q(flat), q(flat_old), q(step), begin, count, int(trial), int(total),
+                                                    float(decay), float(target_kl), q(eval_summary), q(loss_before),
+                                                    q(ng_state), q(ctrl), stream), "cf2_ng_line_search")
+
+
+class NaturalGradientUpdater:
+    """The reference's TRPO (``algorithm="trpo"``) and NPG (``"npg"``) updates on a ``Rollout``: the
+    policy moves along the conjugate-gradient solution of (F + cg_damping I) x = -g, scaled to the KL
+    target; TRPO backtracks over ``line_search_steps`` fractions ``line_search_decay``^j, NPG takes the
+    full step.  The critic is ``ResidentPPOUpdater``'s value phase.
+
+    ``device=True`` (the module and the rollout on the GPU): ``update`` enqueues a fixed sequence of
+    launches on the flat weight block and never waits for the GPU --
+
+        moments   cf2_column_moments of the advantages
+        G0        cf2_ppo_policy_grad with clip_ratio = inf (the unclipped surrogate -mean(ratio A)) on
+                  the starting weights: gradient, LossPi, and mu_old
+        CG        cf2_ng_cg_init, then cg_iters x (cf2_ppo_fisher_vec of p on every fvp_stride-th row,
+                  cf2_ng_cg_step)
+        D         cf2_ppo_fisher_vec of x, cf2_ng_direction: the step, and trial 0 in the weights
+        TRPO      line_search_steps x (gated evaluation with mu_old, cf2_ng_line_search); the launch
+                  that accepts, or that restores the old weights after the last trial, sets the stop
+                  flag, and every later pair returns without writing
+        NPG       one evaluation, for the log
+        value     train_v_iterations passes of num_mini_batches mini-batches, cf2_adam_step (the same
+                  permutations as ``PPOUpdater`` for the same generator)
+
+    and ends with ``unpack_policy_weights`` / ``fused.sync_from_flat``.  ``update(rollout, read=True)``
+    reads the results in one transfer at the end; ``read=False`` returns None without any host
+    synchronisation and ``result()`` reads later.  The policy phase holds no optimiser state;
+    ``state_dict`` carries the value optimiser's.
+
+    ``device=False``: the same loop through ``fisher_vec_torch``, the ``*_torch`` restatements of the
+    solver rules and ``torch.optim.Adam`` for the critic, in the module's dtype on any device: the
+    reference of the tests and the path that runs without a GPU.
+
+    Results: LossPi (before the step), LossV, KL of the kept weights (0 when every trial was
+    rejected; ng_state also holds their loss), AcceptanceStep (accepted trial + 1; 0: all rejected; NPG: 1),
+    StepFrac, xHx, Alpha, ExpectedImprove, CGResidual (|r| after the last CG step), GradNormPi.
+
+    Single rank: the reference averages the gradient and the Fisher-vector product over MPI ranks
+    (``mpi_avg_grads``); that is out of scope here, as it is for ``ResidentPPOUpdater``."""
+
+    KEYS = ("LossPi", "LossV", "KL", "AcceptanceStep", "StepFrac", "xHx", "Alpha", "ExpectedImprove", "CGResidual",
+            "GradNormPi")
+
+    def __init__(self, ac: MLPActorCritic, v_lr: float, target_kl: float, algorithm: str = "trpo", cg_iters: int = 10,
+                 cg_damping: float = 0.1, fvp_stride: int = 4, line_search_steps: int = 25,
+                 line_search_decay: float = 0.8, train_v_iterations: int = 5, num_mini_batches: int = 16,
+                 betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float | None = None, fused=None,
+                 generator: torch.Generator | None = None, device: bool = True):
+        if algorithm not in ("trpo", "npg"):
+            raise ValueError(f"algorithm must be 'trpo' or 'npg', got {algorithm!r}")
+        if fused is not None and fused.ac is not ac:
+            raise ValueError("fused must wrap the same MLPActorCritic")
+        if num_mini_batches < 1 or fvp_stride < 1 or cg_iters < 0 or line_search_steps < 1:
+            raise ValueError("num_mini_batches, fvp_stride and line_search_steps must be at least 1, cg_iters at least 0")
+        if not target_kl >= 0.0 or not cg_damping >= 0.0 or not 0.0 < line_search_decay <= 1.0:
+            raise ValueError("target_kl and cg_damping must not be negative, line_search_decay must lie in (0, 1]")
+        self.ac, self.fused, self.generator, self.algorithm = ac, fused, generator, algorithm
+        self.target_kl, self.cg_iters, self.cg_damping = float(target_kl), int(cg_iters), float(cg_damping)
+        self.fvp_stride, self.line_search_steps = int(fvp_stride), int(line_search_steps)
+        self.line_search_decay = float(line_search_decay)
+        self.train_v_iterations, self.num_mini_batches = int(train_v_iterations), int(num_mini_batches)
+        self.max_grad_norm = 0.0 if max_grad_norm is None else float(max_grad_norm)
+        self.device = bool(device)
+        self._bufs, self._pending, self.flat = None, None, None
+        dev = next(ac.parameters()).device
+        if self.device:
+            if dev.type != "cuda":
+                raise ValueError("NaturalGradientUpdater(device=True) needs the module on the GPU")
+            count = flat_slice(ac, "v")[1] + 2 * ac.pi_net[0].in_features
+            v0, v1 = flat_slice(ac, "v")
+            self.v_optimizer = DeviceAdam(count, v0, v1 - v0, v_lr, betas, eps, max_grad_norm, dev)
+            self.ctrl = torch.zeros(4, dtype=torch.int32, device=dev)
+            self.ng_state = torch.zeros(NG_STATE_DOUBLES, dtype=torch.float64, device=dev)
+            self.summary0, self.summary, self.summary_v, self.summary_mb, self.summary_f = (
+                torch.zeros(8, dtype=torch.float64, device=dev) for _ in range(5))
+            self.work = {k: torch.zeros(count, device=dev) for k in ("b", "x", "r", "p", "z", "step", "old")}
+        else:
+            self.v_optimizer = torch.optim.Adam(ac.v_net.parameters(), lr=v_lr, betas=betas, eps=eps)
+
+    value_minibatches = PPOUpdater.value_minibatches
+    _buffers = PPOUpdater._buffers
+
+    def state_dict(self) -> dict:
+        return {"v": self.v_optimizer.state_dict()}
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.v_optimizer.load_state_dict(sd["v"])
+
+    def result(self) -> dict | None:
+        """The last update's results (one device read); None before the first update."""
+        if self._pending is None:
+            return None
+        out = dict(zip(self.KEYS, self._pending.tolist() if isinstance(self._pending, torch.Tensor) else self._pending))
+        out["AcceptanceStep"] = int(out["AcceptanceStep"])
+        return out
+
+    def update(self, rollout: Rollout, read: bool = True) -> dict | None:
+        d = rollout.obs.shape[-1]
+        obs, act = rollout.obs.reshape(-1, d), rollout.act.reshape(-1, 4)
+        logp_old, adv, ret = rollout.logp.reshape(-1), rollout.adv.reshape(-1), rollout.ret.reshape(-1)
+        n = obs.shape[0]
+        if n == 0 or n >= 2 ** 31:
+            raise ValueError(f"a rollout of {n} rows cannot be updated from in one call")
+        if self.device:
+            self._update_device(obs, act, logp_old, adv, ret)
+        else:
+            self._update_torch(obs, act, logp_old, adv, ret)
+            if self.fused is not None:
+                self.fused.sync()
+        return self.result() if read else None
+
+    # ---- the launches
+    @torch.no_grad()
+    def _update_device(self, obs, act, logp_old, adv, ret) -> None:
+        from . import _native
+        from .rollout import unpack_policy_weights
+        ac, inf, kl_t, damp = self.ac, float("inf"), self.target_kl, self.cg_damping
+        obs, act, logp_old, adv, ret = (t.contiguous() for t in (obs, act, logp_old, adv, ret))
+        n, d, dev = obs.shape[0], obs.shape[1], obs.device
+        B = self._buffers(n, d, dev)
+        scratch, grad, mu_old, mom = B["scratch"], B["grad"], B["mu_old"], B["moments"]
+        if "fvp_idx" not in B or B["fvp_stride"] != self.fvp_stride:
+            B["fvp_idx"] = torch.arange(0, n, self.fvp_stride, dtype=torch.int32, device=dev)
+            B["fvp_stride"] = self.fvp_stride
+        fidx = B["fvp_idx"]
+        summary0, summary, ctrl, st, W = self.summary0, self.summary, self.ctrl, self.ng_state, self.work
+        lib = _native.load()
+        _native.check(lib.cf2_column_moments(adv.data_ptr(), n, 1, mom.data_ptr(), scratch.data_ptr(),
+                                             torch.cuda.current_stream(dev).cuda_stream), "cf2_column_moments")
+        flat = pack_policy_weights(ac)
+        ctrl.zero_()
+        p0, p1 = flat_slice(ac, "pi")
+        pol = lambda summ, **kw: policy_grad_device(flat, obs, act, logp_old, adv, inf, summ, scratch, adv_moments=mom, **kw)
+        fvp = lambda vec: fisher_vec_device(flat, obs, vec, W["z"], self.summary_f, scratch, idx=fidx)
+        value_grad_device(flat, obs, ret, self.summary_v, scratch)
+        pol(summary0, mu_out=mu_old, grad=grad)
+        ng_cg_init_device(grad, W["b"], W["x"], W["r"], W["p"], p0, p1 - p0, st)
+        for _ in range(self.cg_iters):
+            fvp(W["p"])
+            ng_cg_step_device(W["z"], W["x"], W["r"], W["p"], p0, p1 - p0, damp, st)
+        fvp(W["x"])
+        ng_direction_device(W["z"], W["x"], W["b"], W["step"], flat, W["old"], p0, p1 - p0, damp, kl_t, st)
+        if self.algorithm == "trpo":
+            for j in range(self.line_search_steps):
+                pol(summary, mu_old=mu_old, ctrl=ctrl)
+                ng_line_search_device(flat, W["old"], W["step"], p0, p1 - p0, j, self.line_search_steps,
+                                      self.line_search_decay, kl_t, summary, summary0[1:2], st, ctrl)
+            after = [st[NG_KL_AFTER:NG_KL_AFTER + 1], st[NG_ACCEPT_STEP:NG_ACCEPT_STEP + 1],
+                     st[NG_STEP_FRAC:NG_STEP_FRAC + 1]]
+        else:
+            pol(summary, mu_old=mu_old)
+            one = torch.ones(1, dtype=torch.float64, device=dev)
+            after = [summary[4:5], one, one]
+        for _ in range(self.train_v_iterations):
+            for mb in self.value_minibatches(n, dev):
+                idx = B["idx"][:mb.shape[0]]
+                idx.copy_(mb)
+                value_grad_device(flat, obs, ret, self.summary_mb, scratch, grad=grad, idx=idx)
+                self.v_optimizer.step(flat, grad)
+        unpack_policy_weights(ac, flat)
+        if self.fused is not None:
+            self.fused.sync_from_flat(flat)
+        self.flat = flat
+        self._pending = torch.cat([summary0[1:2], self.summary_v[1:2], after[0], after[1], after[2], st[NG_XHX:NG_XHX + 1],
+                                   st[NG_ALPHA:NG_ALPHA + 1], st[NG_EXPECTED:NG_EXPECTED + 1],
+                                   st[NG_RESIDUAL:NG_RESIDUAL + 1].sqrt(), st[NG_BDOTB:NG_BDOTB + 1].sqrt()])
+
+    # ---- torch autograd (the fall-back, and the reference of the tests)
+    def _update_torch(self, obs, act, logp_old, adv, ret) -> None:
+        ac, inf, kl_t, damp = self.ac, float("inf"), self.target_kl, self.cg_damping
+        n, dev = obs.shape[0], obs.device
+        params = [p for m in _linears(ac, "pi") for p in (m.weight, m.bias)]
+        with torch.no_grad():
+            a64 = adv.double()
+            mean = a64.mean()
+            std = torch.sqrt(((a64 - mean) ** 2).sum() / n)
+            adv = ((a64 - mean) / (std + 1e-8)).to(obs.dtype)
+            mu_old = policy_terms_torch(ac, obs, act, logp_old, adv, inf)["mu"]
+            loss_v = float(value_loss_torch(ac, obs, ret))
+
+        def evaluate():
+            with torch.no_grad():
+                t = policy_terms_torch(ac, obs, act, logp_old, adv, inf, mu_old=mu_old)
+                return float(t["rows"].double().mean()), float(t["kl"].double().mean())
+
+        rows = policy_terms_torch(ac, obs, act, logp_old, adv, inf)["rows"]
+        g = pi_flat(ac, torch.autograd.grad(rows.mean(), params))
+        loss_before = float(rows.detach().double().mean())
+        sub = obs[::self.fvp_stride]
+        st = cg_init_torch(g)
+        for _ in range(self.cg_iters):
+            cg_step_torch(st, fisher_vec_torch(ac, sub, st["p"]), damp)
+        direction_torch(st, fisher_vec_torch(ac, sub, st["x"]), damp, kl_t)
+        theta_old = pi_flat(ac).clone()
+        set_pi_flat(ac, theta_old + st["step"])
+        if self.algorithm == "trpo":
+            total, decay = self.line_search_steps, self.line_search_decay
+            for j in range(total):
+                loss_j, kl_j = evaluate()
+                what, frac = line_search_torch(j, total, decay, kl_t, loss_j, kl_j, loss_before)
+                if what == "accept":
+                    after = (kl_j, j + 1, frac)
+                    break
+                if what == "retry":
+                    set_pi_flat(ac, theta_old + frac * st["step"])
+                else:
+                    set_pi_flat(ac, theta_old)
+                    after = (0.0, 0, 0.0)
+        else:
+            loss_j, kl_j = evaluate()
+            after = (kl_j, 1, 1.0)
+        for _ in range(self.train_v_iterations):
+            for mb in self.value_minibatches(n, dev):
+                self.v_optimizer.zero_grad()
+                value_loss_torch(ac, obs[mb], ret[mb]).backward()
+                if self.max_grad_norm > 0.0:
+                    nn.utils.clip_grad_norm_(ac.v_net.parameters(), self.max_grad_norm)
+                self.v_optimizer.step()
+        self._pending = [loss_before, loss_v, after[0], after[1], after[2], float(st["xHx"]), float(st["alpha"]),
+                         float(st["expected"]), float(torch.sqrt(st["residual"])), float(torch.sqrt(st["bdotb"]))]
+
+
 __all__ = ["policy_loss_torch", "policy_terms_torch", "value_loss_torch", "scatter_flat_grad", "flat_slice",
            "policy_grad_device", "value_grad_device", "adam_step_device", "DeviceAdam", "PPOUpdater",
-           "ResidentPPOUpdater"]
+           "ResidentPPOUpdater", "pi_flat", "pi_unflat", "set_pi_flat", "fisher_vec_torch", "cg_init_torch",
+           "cg_step_torch", "direction_torch", "line_search_torch", "fisher_vec_device", "ng_cg_init_device",
+           "ng_cg_step_device", "ng_direction_device", "ng_line_search_device", "NaturalGradientUpdater"]

@@ -562,6 +562,407 @@ static int ppo_launch(PpoArgs a, float* grad, double* summary, void* scratch, hi
 
 static bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1u)) != 0; }
 
+// ---------------------------------------------------------------------------------------------
+// Fisher-vector product of the policy (the natural-gradient updates, cf2sim_natgrad.hip).  For a
+// Gaussian policy whose log_std is not trained the KL to the old policy is
+// sum_k (mu_old_k - mu_k)^2 / (2 sigma_k^2); its Hessian at mu = mu_old is the Gauss-Newton matrix
+// F = (1/m) sum_rows J^T Sigma^-1 J exactly (the term with the net's second derivatives is multiplied
+// by mu - mu_old = 0).  F v per 16-row tile: the primal forward of ppo_kernel up to h2, a tangent
+// pass with the weights' direction v = (V1 vb1 V2 vb2 V3 vb3) riding on the same B operands,
+//     th1 = relu'(z1) (V1^T z + vb1)
+//     th2 = relu'(z2) (V2^T h1 + W2^T th1 + vb2)
+//     tmu = V3^T h2 + W3^T th2 + vb3                           (= J v, on the VALU like layer 3)
+// then dout = tmu / sigma^2 through the backward pass and the gradient GEMMs of ppo_kernel.  The
+// tangents are dead once tmu is known, so the accumulators, the block reduction and ppo_merge_kernel
+// are the gradient kernel's; the direction needs a second zero-padded LDS copy (the map of the
+// weights, moved behind the waves' staging tiles).  summary[1] = v^T F v = mean_rows sum_k tmu_k^2 /
+// sigma_k^2, in fp64.
+// ---------------------------------------------------------------------------------------------
+struct FisherArgs {
+    const float* W;
+    const float* V;              // the direction: a whole flat block, the words [P_W1, P_LOGSTD) are read
+    const float* obs;
+    const uint32_t* idx;
+    double* part_sum;            // [blocks][PPO_SUM]
+    float* part_grad;            // [blocks][NPAR]
+    uint32_t n, m;
+    const uint32_t* gate;        // as PpoArgs::gate
+};
+
+template <int D>
+__global__ void __launch_bounds__(PPO_BLOCK) ppo_fisher_kernel(const FisherArgs a) {
+    using N = PpoNet<D, true>;
+    using L = PolicyLayout<D>;
+    constexpr int H = N::H, NO = N::NO, WS = PPO_WS, AS = PPO_AS, ZS = PPO_ZS;
+    constexpr int TAN = N::LDS_FLOATS;             // the direction's copy: the map of the weights, shifted
+    constexpr int TAN_FLOATS = N::S_MEAN;          // W1 W2 W3 b1 b2 b3
+    if (a.gate && *a.gate != 0u) return;
+    __shared__ __attribute__((aligned(16))) float lds[N::LDS_FLOATS + TAN_FLOATS];
+    __shared__ double sred[PPO_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
+    float* W1s = lds + N::S_W1;
+    float* W2s = lds + N::S_W2;
+    float* W3s = lds + N::S_W3;
+    float* b1s = lds + N::S_B1;
+    float* b2s = lds + N::S_B2;
+    float* V1s = lds + TAN + N::S_W1;
+    float* V2s = lds + TAN + N::S_W2;
+    float* V3s = lds + TAN + N::S_W3;
+    float* vb1s = lds + TAN + N::S_B1;
+    float* vb2s = lds + TAN + N::S_B2;
+    float* vb3s = lds + TAN + N::S_B3;
+    float* means = lds + N::S_MEAN;
+    float* scales = lds + N::S_SCALE;
+    float* Z = lds + N::S_WAVE + wave * N::WAVE_FLOATS + N::WAVE_Z;
+    float* ACT = lds + N::S_WAVE + wave * N::WAVE_FLOATS + N::WAVE_ACT;
+    float* DZ = lds + N::S_WAVE + wave * N::WAVE_FLOATS + N::WAVE_DZ;
+
+    // ---- the net's weights and the direction, zero-padded to 64 neurons per layer
+    const float* Wn = a.W + N::BASE;
+    const float* Vn = a.V + N::BASE;
+    for (int e = tid; e < N::KP1 * 64; e += PPO_BLOCK) {
+        const int k = e >> 6, n = e & 63;
+        const bool in = k < D && n < H;
+        W1s[k * WS + n] = in ? Wn[N::W1 + k * H + n] : 0.0f;
+        V1s[k * WS + n] = in ? Vn[N::W1 + k * H + n] : 0.0f;
+    }
+    for (int e = tid; e < 64 * 64; e += PPO_BLOCK) {
+        const int k = e >> 6, n = e & 63;
+        const bool in = k < H && n < H;
+        W2s[k * WS + n] = in ? Wn[N::W2 + k * H + n] : 0.0f;
+        V2s[k * WS + n] = in ? Vn[N::W2 + k * H + n] : 0.0f;
+    }
+    {
+        const int k = tid >> 2, o = tid & 3;
+        const bool in = k < H && o < NO;
+        W3s[tid] = in ? Wn[N::W3 + k * NO + o] : 0.0f;
+        V3s[tid] = in ? Vn[N::W3 + k * NO + o] : 0.0f;
+    }
+    if (tid < 64) {
+        b1s[tid] = tid < H ? Wn[N::B1 + tid] : 0.0f;
+        b2s[tid] = tid < H ? Wn[N::B2 + tid] : 0.0f;
+        vb1s[tid] = tid < H ? Vn[N::B1 + tid] : 0.0f;
+        vb2s[tid] = tid < H ? Vn[N::B2 + tid] : 0.0f;
+        if (tid < 4) vb3s[tid] = tid < NO ? Vn[N::B3 + tid] : 0.0f;
+        if (tid < 48) {
+            means[tid] = tid < D ? a.W[L::O_MEAN + tid] : 0.0f;
+            scales[tid] = tid < D ? a.W[L::O_SCALE + tid] : 0.0f;
+        }
+    }
+    for (int e = lane; e < 16 * ZS; e += 64) Z[e] = 0.0f;        // the columns past D stay 0
+    __syncthreads();
+
+    // ---- per-lane constants
+    float inv_var[4];
+    double inv_var64[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        inv_var64[k] = exp(-2.0 * (double)a.W[L::P_LOGSTD + k]);
+        inv_var[k] = (float)inv_var64[k];
+    }
+
+    // ---- accumulators
+    f4v acc1[N::KT1][4], acc2[4][4];
+    float w3acc[4][4][NO], b1acc[4][4], b2acc[4][4], b3acc[NO];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int kt = 0; kt < N::KT1; ++kt) acc1[kt][t] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) acc2[kt][t] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            b1acc[t][i] = 0.0f;
+            b2acc[t][i] = 0.0f;
+#pragma unroll
+            for (int o = 0; o < NO; ++o) w3acc[t][i][o] = 0.0f;
+        }
+    }
+#pragma unroll
+    for (int o = 0; o < NO; ++o) b3acc[o] = 0.0f;
+    double S = 0.0;
+
+    const uint32_t ntiles = (a.m + 15u) / 16u, nwaves = gridDim.x * PPO_WAVES;
+    // the row of position 16 tile + c; a position past m reads row m - 1 and contributes nothing
+    auto row_of = [&](uint32_t tile) {
+        const uint32_t jc = __builtin_elementwise_min(tile * 16u + (uint32_t)c, a.m - 1u);
+        return a.idx ? __builtin_elementwise_min(a.idx[jc], a.n - 1u) : jc;
+    };
+    constexpr int ZIT = (16 * D + 63) / 64;
+    float xr[ZIT];
+    auto load_obs = [&](uint32_t row) {
+#pragma unroll
+        for (int it = 0; it < ZIT; ++it) {
+            const int e = it * 64 + lane, ee = e < 16 * D ? e : 16 * D - 1;
+            const int r = ee / D, k = ee - r * D;
+            xr[it] = a.obs[(size_t)__shfl(row, r) * D + k];
+        }
+    };
+    uint32_t tile = blockIdx.x * PPO_WAVES + wave;
+    uint32_t row = row_of(tile < ntiles ? tile : ntiles - 1u);
+    load_obs(row);
+    for (; tile < ntiles; tile += nwaves) {
+        const uint32_t j = tile * 16u + (uint32_t)c;
+        const bool valid = j < a.m;
+#pragma unroll
+        for (int it = 0; it < ZIT; ++it) {
+            const int e = it * 64 + lane, ee = e < 16 * D ? e : 16 * D - 1;
+            const int r = ee / D, k = ee - r * D;
+            if (e < 16 * D) Z[r * ZS + k] = (xr[it] - means[k]) * scales[k];
+        }
+        wave_lds_sync();
+        {
+            const uint32_t next = tile + nwaves;
+            row = row_of(next < ntiles ? next : ntiles - 1u);
+            load_obs(row);
+        }
+
+        // ---- layer 1 and its tangent: the same B operand
+        f4v h1[4], h2[4], t1[4], t2[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                h1[t][i] = b1s[16 * t + 4 * g + i];
+                t1[t][i] = vb1s[16 * t + 4 * g + i];
+            }
+#pragma unroll
+        for (int s = 0; s < N::KS1; ++s) {
+            const float b = Z[c * ZS + 4 * s + g];
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                h1[nt] = mfma4(W1s[(4 * s + g) * WS + 16 * nt + c], b, h1[nt]);
+                t1[nt] = mfma4(V1s[(4 * s + g) * WS + 16 * nt + c], b, t1[nt]);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                h1[t][i] = relu(h1[t][i]);
+                t1[t][i] = ppo_dact<true>(h1[t][i], t1[t][i]);
+            }
+        // ---- layer 2: k-step (t, i) holds the inputs 16t + 4g + i
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                h2[t][i] = b2s[16 * t + 4 * g + i];
+                t2[t][i] = vb2s[16 * t + 4 * g + i];
+            }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (16 * t + i >= H) continue;
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) {
+                    const float w = W2s[(16 * t + 4 * g + i) * WS + 16 * nt + c];
+                    h2[nt] = mfma4(w, h1[t][i], h2[nt]);
+                    t2[nt] = mfma4(V2s[(16 * t + 4 * g + i) * WS + 16 * nt + c], h1[t][i], t2[nt]);
+                    t2[nt] = mfma4(w, t1[t][i], t2[nt]);
+                }
+            }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                h2[t][i] = relu(h2[t][i]);
+                t2[t][i] = ppo_dact<true>(h2[t][i], t2[t][i]);
+            }
+        // ---- J v on the VALU: this lane's 16 neurons, then the four lane groups
+        float tmu[NO];
+#pragma unroll
+        for (int o = 0; o < NO; ++o) tmu[o] = 0.0f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int o = 0; o < NO; ++o) {
+                    tmu[o] = fmaf(h2[t][i], V3s[(16 * t + 4 * g + i) * 4 + o], tmu[o]);
+                    tmu[o] = fmaf(t2[t][i], W3s[(16 * t + 4 * g + i) * 4 + o], tmu[o]);
+                }
+        float dout[NO];
+#pragma unroll
+        for (int o = 0; o < NO; ++o) {
+            tmu[o] += __shfl_xor(tmu[o], 16);
+            tmu[o] += __shfl_xor(tmu[o], 32);
+            tmu[o] += vb3s[o];
+            dout[o] = valid ? tmu[o] * inv_var[o] : 0.0f;
+        }
+        if (valid && g == 0) {                     // one lane per row counts
+#pragma unroll
+            for (int o = 0; o < NO; ++o) S += (double)tmu[o] * (double)tmu[o] * inv_var64[o];
+        }
+
+        // ---- layer 3 backward (per lane), dZ2
+        f4v dz2[4], dz1[4];
+#pragma unroll
+        for (int o = 0; o < NO; ++o) b3acc[o] += dout[o];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float dh = 0.0f;
+#pragma unroll
+                for (int o = 0; o < NO; ++o) {
+                    w3acc[t][i][o] = fmaf(h2[t][i], dout[o], w3acc[t][i][o]);
+                    dh = fmaf(dout[o], W3s[(16 * t + 4 * g + i) * 4 + o], dh);
+                }
+                dz2[t][i] = ppo_dact<true>(h2[t][i], dh);
+                b2acc[t][i] += dz2[t][i];
+            }
+        // ---- dW2 += H1^T dZ2 over the tile's rows: both through the staging tile [row][neuron]
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                ACT[c * AS + 16 * t + 4 * g + i] = h1[t][i];
+                DZ[c * AS + 16 * t + 4 * g + i] = dz2[t][i];
+            }
+        wave_lds_sync();
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            float av[4], bv[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                av[t] = ACT[(4 * s + g) * AS + 16 * t + c];
+                bv[t] = DZ[(4 * s + g) * AS + 16 * t + c];
+            }
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) acc2[kt][nt] = mfma4(av[kt], bv[nt], acc2[kt][nt]);
+        }
+        // ---- dH1^T = W2 dZ2^T, dZ1
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) dz1[kt] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (16 * t + i >= H) continue;
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt)
+                    dz1[kt] = mfma4(W2s[(16 * kt + c) * WS + 16 * t + 4 * g + i], dz2[t][i], dz1[kt]);
+            }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                dz1[t][i] = ppo_dact<true>(h1[t][i], dz1[t][i]);
+                b1acc[t][i] += dz1[t][i];
+            }
+        // ---- dW1 += Z^T dZ1
+        wave_lds_sync();                           // every lane has read dZ2 from the staging tile
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) DZ[c * AS + 16 * t + 4 * g + i] = dz1[t][i];
+        wave_lds_sync();
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            float av[N::KT1], bv[4];
+#pragma unroll
+            for (int kt = 0; kt < N::KT1; ++kt) av[kt] = Z[(4 * s + g) * ZS + 16 * kt + c];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) bv[t] = DZ[(4 * s + g) * AS + 16 * t + c];
+#pragma unroll
+            for (int kt = 0; kt < N::KT1; ++kt)
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) acc1[kt][nt] = mfma4(av[kt], bv[nt], acc1[kt][nt]);
+        }
+        wave_lds_sync();                           // the next tile overwrites Z and the staging tile
+    }
+
+    // ---- the block's summary: lanes, then waves, in a fixed order
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) S += __shfl_xor(S, d);
+    if (lane == 0) sred[wave] = S;
+    __syncthreads();                               // also: every wave is done with the weights in LDS
+    if (tid < PPO_SUM) {
+        double v = 0.0;
+        if (tid == 1)
+            for (int w = 0; w < PPO_WAVES; ++w) v += sred[w];
+        a.part_sum[(size_t)blockIdx.x * PPO_SUM + tid] = v;
+    }
+
+    // ---- the block's product: the waves add into LDS in wave order (wave 0 stores)
+    float* red = lds;
+    float db3[NO];
+#pragma unroll
+    for (int o = 0; o < NO; ++o) db3[o] = sum_rows(b3acc[o]);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            b1acc[t][i] = sum_rows(b1acc[t][i]);
+            b2acc[t][i] = sum_rows(b2acc[t][i]);
+#pragma unroll
+            for (int o = 0; o < NO; ++o) w3acc[t][i][o] = sum_rows(w3acc[t][i][o]);
+        }
+    for (int w = 0; w < PPO_WAVES; ++w) {
+        if (wave == w) {
+            const bool first = w == 0;
+            auto put = [&](int p, float v) { red[p] = first ? v : red[p] + v; };
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                const int n = 16 * nt + c;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                    for (int kt = 0; kt < N::KT1; ++kt) {
+                        const int k = 16 * kt + 4 * g + i;
+                        if (k < D && n < H) put(N::W1 + k * H + n, acc1[kt][nt][i]);
+                    }
+#pragma unroll
+                    for (int kt = 0; kt < 4; ++kt) {
+                        const int k = 16 * kt + 4 * g + i;
+                        if (k < H && n < H) put(N::W2 + k * H + n, acc2[kt][nt][i]);
+                    }
+                }
+            }
+            if (c == 0) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int k = 16 * t + 4 * g + i;
+                        if (k < H) {
+                            put(N::B1 + k, b1acc[t][i]);
+                            put(N::B2 + k, b2acc[t][i]);
+#pragma unroll
+                            for (int o = 0; o < NO; ++o) put(N::W3 + k * NO + o, w3acc[t][i][o]);
+                        }
+                    }
+                if (g == 0) {
+#pragma unroll
+                    for (int o = 0; o < NO; ++o) put(N::B3 + o, db3[o]);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    float* dst = a.part_grad + (size_t)blockIdx.x * N::NPAR;
+    for (int p = tid; p < N::NPAR; p += PPO_BLOCK) dst[p] = red[p];
+}
+
+template <int D>
+static int fisher_launch(FisherArgs a, float* out, double* summary, void* scratch, hipStream_t s) {
+    using N = PpoNet<D, true>;
+    const uint32_t blocks = ppo_blocks(a.m);
+    a.part_sum = static_cast<double*>(scratch);
+    a.part_grad = reinterpret_cast<float*>(a.part_sum + (size_t)PPO_MAX_BLOCKS * PPO_SUM);
+    hipLaunchKernelGGL((ppo_fisher_kernel<D>), dim3(blocks), dim3(PPO_BLOCK), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e);
+    hipLaunchKernelGGL(ppo_merge_kernel, dim3((N::NPAR + 255u) / 256u), dim3(256), 0, s, a.part_grad, a.part_sum, blocks,
+                       (uint32_t)N::NPAR, a.m, out + N::BASE, summary, a.gate);
+    e = hipGetLastError();
+    return e == hipSuccess ? CF2_OK : hip_fail(e);
+}
+
 }  // namespace cf2
 
 using namespace cf2;
@@ -629,4 +1030,20 @@ extern "C" int cf2_ppo_value_grad(const float* weights_dev, uint32_t obs_dim, co
     const hipStream_t s = (hipStream_t)stream;
     return obs_dim == 34 ? ppo_launch<34, false>(a, grad_dev, summary_dev, scratch_dev, s)
                          : ppo_launch<42, false>(a, grad_dev, summary_dev, scratch_dev, s);
+}
+
+extern "C" int cf2_ppo_fisher_vec(const float* weights_dev, uint32_t obs_dim, const float* obs_dev, uint32_t n,
+                                  const uint32_t* idx_dev, uint32_t m, const float* vec_dev, float* out_dev,
+                                  double* summary_dev, void* scratch_dev, const uint32_t* ctrl_dev, void* stream) {
+    if (obs_dim != 34 && obs_dim != 42) return CF2_ERR_UNSUPPORTED;
+    if (m == 0) return CF2_OK;
+    if (!weights_dev || !obs_dev || !vec_dev || !out_dev || !summary_dev || !scratch_dev || n == 0 || (!idx_dev && m > n))
+        return CF2_ERR_INVALID_ARG;
+    if (misaligned(weights_dev, 4) || misaligned(obs_dev, 8) || misaligned(idx_dev, 4) || misaligned(vec_dev, 4) ||
+        misaligned(out_dev, 4) || misaligned(summary_dev, 8) || misaligned(scratch_dev, 8) || misaligned(ctrl_dev, 4))
+        return CF2_ERR_INVALID_ARG;
+    FisherArgs a = {weights_dev, vec_dev, obs_dev, idx_dev, nullptr, nullptr, n, m, ctrl_dev};
+    const hipStream_t s = (hipStream_t)stream;
+    return obs_dim == 34 ? fisher_launch<34>(a, out_dev, summary_dev, scratch_dev, s)
+                         : fisher_launch<42>(a, out_dev, summary_dev, scratch_dev, s);
 }

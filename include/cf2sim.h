@@ -473,6 +473,96 @@ int  cf2_adam_step(float* weights_dev, const float* grad_dev, float* exp_avg_dev
                    float max_grad_norm, double* norm_out_dev, const double* kl_summary_dev, float target_kl,
                    uint32_t* ctrl_dev, void* stream);
 
+/* Fisher-vector product of the policy, out = F vec, for the natural-gradient updates (algs/npg,
+ * algs/trpo: the Hessian-vector product of the mean KL to the detached policy).  The policy is
+ * Gaussian with an untrained log_std, so KL = sum_k (mu_old_k - mu_k)^2 / (2 sigma_k^2) and its Hessian
+ * at mu = mu_old is exactly the Gauss-Newton matrix F = (1/m) sum_rows J^T Sigma^-1 J (J = d mu / d
+ * parameters; the term with the network's second derivatives is multiplied by mu - mu_old = 0).  One
+ * fused launch (the primal forward, a tangent pass J vec, dout = J vec / sigma^2, the backward pass
+ * and gradient GEMMs of cf2_ppo_policy_grad) plus the merge launch.  No damping is added.
+ * weights_dev: the flat block, obs_dim 34 or 42; obs [n, obs_dim] (8-byte aligned); idx_dev / m as in
+ * the gradient calls (the reference takes every fourth row, obs[::4]: idx = 0, 4, 8, ...).
+ * vec_dev and out_dev are whole flat blocks: the call reads the words [P_W1, P_LOGSTD) of vec and
+ * writes exactly those words of out; every other word is left untouched.  ReLU' is 0 at a
+ * pre-activation <= 0.  summary_dev, 8 doubles: [0] m, [1] vec^T F vec = mean_rows sum_k (J vec)_k^2 /
+ * sigma_k^2 accumulated in fp64, [2..7] 0.  ctrl_dev: the gate of cf2_ppo_policy_grad_gated (NULL or
+ * ctrl_dev[0] == 0: run; otherwise both launches return at once and out, summary and the scratch are
+ * left untouched).  scratch_dev: cf2_ppo_scratch_bytes(m, obs_dim) bytes, 8-byte aligned.  Products
+ * are exact fp32, block partials are merged in block-index order in fp64, divided by m and rounded
+ * once: no atomics, the same input gives the same bits.  obs_dim not 34 or 42: CF2_ERR_UNSUPPORTED;
+ * m == 0: CF2_OK, nothing launched or written; a NULL weights, obs, vec, out, summary or scratch
+ * pointer, a misaligned pointer, n == 0 or idx_dev == NULL with m > n: CF2_ERR_INVALID_ARG.  Every
+ * error returns before anything is launched. */
+int  cf2_ppo_fisher_vec(const float* weights_dev, uint32_t obs_dim, const float* obs_dev, uint32_t n,
+                        const uint32_t* idx_dev, uint32_t m, const float* vec_dev, float* out_dev,
+                        double* summary_dev, void* scratch_dev, const uint32_t* ctrl_dev, void* stream);
+
+/* The solver of the natural-gradient updates on a slice [begin, begin + count) of flat blocks, with
+ * every scalar on the device: ng_state_dev, CF2_NG_STATE_DOUBLES doubles. */
+enum { CF2_NG_RDOTR = 0,        /* r.r of the conjugate-gradient recurrence (cg_init: b.b) */
+       CF2_NG_CG_STEPS = 1,     /* cg_step calls applied since cg_init */
+       CF2_NG_CG_DONE = 2,      /* 1 once sqrt(r.r) < 1e-10: later cg_step calls write nothing */
+       CF2_NG_XHX = 3,          /* direction: x.(F x + damping x) */
+       CF2_NG_ALPHA = 4,        /* direction: sqrt(2 target_kl / (xHx + 1e-8)) */
+       CF2_NG_EXPECTED = 5,     /* direction: b.step, the expected improvement of the full step */
+       CF2_NG_STEP_FRAC = 6,    /* line search: decay^trial of the accepted trial; 0: all rejected */
+       CF2_NG_ACCEPT_STEP = 7,  /* line search: accepted trial + 1; 0: all rejected */
+       CF2_NG_LOSS_BEFORE = 8,  /* line search: *loss_before_dev */
+       CF2_NG_LOSS_AFTER = 9,   /* line search: loss of the accepted trial; all rejected: loss before */
+       CF2_NG_KL_AFTER = 10,    /* line search: KL of the accepted trial; all rejected: 0 */
+       CF2_NG_PDOTZ = 11,       /* p.(z + damping p) of the last applied cg_step */
+       CF2_NG_BDOTB = 12,       /* cg_init: b.b = |grad|^2 over the slice */
+       CF2_NG_RESIDUAL = 13,    /* r.r after the last applied cg_step, the converging one included */
+       CF2_NG_STATE_DOUBLES = 16 /* 14, 15: reserved, zeroed by cg_init */ };
+/* All four calls: one launch of one workgroup that strides over the slice; the vectors (grad, b, x, r,
+ * p, z, step, weights, weights_old) are whole flat blocks of which only the words [begin, begin +
+ * count) are read or written.  Dot products are fp64 sums of fp64 products of the fp32 words in a
+ * fixed order; every written word is evaluated in fp64 from the fp32 values and rounded once; a dot
+ * product after an update reads the rounded words.  The scalars passed as float (damping, target_kl,
+ * decay) enter as the fp32 values.  No atomics; the same input gives the same bits.  ctrl_dev is the
+ * control block of cf2_adam_step; in cg_init, cg_step and direction it is an optional read-only gate
+ * (ctrl_dev[0] != 0: return, nothing written).  count == 0: CF2_OK, nothing launched; a NULL pointer
+ * (every pointer but the gate is required), a misaligned one (4 bytes; 8 for ng_state, eval_summary
+ * and loss_before), begin + count past 32 bits, damping or target_kl negative or not finite, decay
+ * outside (0, 1], trial >= total: CF2_ERR_INVALID_ARG; count > 2^20: CF2_ERR_UNSUPPORTED.  Every
+ * error returns before anything is launched.
+ *
+ * cf2_ng_cg_init: b = -grad, x = 0, r = p = b; ng_state: RDOTR = BDOTB = RESIDUAL = b.b, every other
+ * word (CG_DONE included) 0.
+ *
+ * cf2_ng_cg_step, given z = F p (cf2_ppo_fisher_vec of p): if CG_DONE is set, return with nothing
+ * written.  z' = z + damping p; a = RDOTR / (p.z' + 1e-6); x += a p; r -= a z'; new = r.r;
+ * ++CG_STEPS, RESIDUAL = new, PDOTZ = p.z'; if sqrt(new) < 1e-10: CG_DONE = 1 and p, RDOTR stay;
+ * otherwise p = r + new / (RDOTR + 1e-6) p and RDOTR = new.  z' is not stored.
+ *
+ * cf2_ng_direction, given z = F x: XHX = x.(z + damping x); ALPHA = sqrt(2 target_kl / (XHX + 1e-8));
+ * step = ALPHA x; EXPECTED = b.step; weights_old = weights; weights = weights_old + step (trial 0).
+ * A negative XHX + 1e-8 gives NaN, as the reference's; there is no special case.
+ *
+ * cf2_ng_line_search, trial `trial` of `total` (0-based), given the policy summary of the weights of
+ * that trial (eval_summary_dev: cf2_ppo_policy_grad_gated with mu_old; [1] loss, [4] KL) and
+ * *loss_before_dev (e.g. word 1 of the summary on the starting weights).  ctrl_dev is required.
+ *   1. ctrl_dev[0] != 0: return, nothing written.
+ *   2. accept iff the loss is finite, loss_before - loss >= 0 and KL <= 1.5 (double)target_kl (a NaN
+ *      fails each): ctrl_dev[0] = 1, ctrl_dev[1] = trial + 1, STEP_FRAC = decay^trial, ACCEPT_STEP =
+ *      trial + 1, LOSS_BEFORE, LOSS_AFTER = loss, KL_AFTER = KL; the weights stay.
+ *   3. rejected and trial + 1 < total: weights = weights_old + decay^(trial + 1) step (the power by
+ *      repeated squaring in fp64); nothing else written.
+ *   4. the last trial rejected: weights = weights_old bit for bit, STEP_FRAC = ACCEPT_STEP = 0,
+ *      KL_AFTER = 0, LOSS_AFTER = LOSS_BEFORE = loss before, ctrl_dev[0] = 1.
+ * Nothing but this launch and cf2_adam_step writes the stop flag. */
+int  cf2_ng_cg_init(const float* grad_dev, float* b_dev, float* x_dev, float* r_dev, float* p_dev, uint32_t begin,
+                    uint32_t count, double* ng_state_dev, const uint32_t* ctrl_dev, void* stream);
+int  cf2_ng_cg_step(const float* z_dev, float* x_dev, float* r_dev, float* p_dev, uint32_t begin, uint32_t count,
+                    float damping, double* ng_state_dev, const uint32_t* ctrl_dev, void* stream);
+int  cf2_ng_direction(const float* z_dev, const float* x_dev, const float* b_dev, float* step_dev, float* weights_dev,
+                      float* weights_old_dev, uint32_t begin, uint32_t count, float damping, float target_kl,
+                      double* ng_state_dev, const uint32_t* ctrl_dev, void* stream);
+int  cf2_ng_line_search(float* weights_dev, const float* weights_old_dev, const float* step_dev, uint32_t begin,
+                        uint32_t count, uint32_t trial, uint32_t total, float decay, float target_kl,
+                        const double* eval_summary_dev, const double* loss_before_dev, double* ng_state_dev,
+                        uint32_t* ctrl_dev, void* stream);
+
 /* Multi-GPU observation exchange as deltas (the north star's per-step RCCL
  * all-gather of the obs slab).  The reference has no counterpart: its MPI ranks exchange only
  * gradients and statistics (utils/mpi_tools.py:30-44); the rows materialised here are exactly what
