@@ -30,6 +30,8 @@ EXPORTED_SYMBOLS = (
     "cf2_episode_stats_scratch_bytes", "cf2_episode_stats", "cf2_column_moments_scratch_bytes", "cf2_column_moments",
     "cf2_ppo_scratch_bytes", "cf2_ppo_policy_grad", "cf2_ppo_value_grad", "cf2_ppo_policy_grad_gated", "cf2_adam_step",
     "cf2_ppo_fisher_vec", "cf2_ng_cg_init", "cf2_ng_cg_step", "cf2_ng_direction", "cf2_ng_line_search",
+    "cf2_ppo_partial_doubles", "cf2_ppo_policy_partial", "cf2_ppo_value_partial", "cf2_ppo_fisher_partial", "cf2_ppo_reduce",
+    "cf2_column_moments_partial", "cf2_moments_combine",
     "cf2_hbm_probe", "cf2_step_packed", "cf2_obs_packed_words", "cf2_xchg_send_words", "cf2_obs_pack", "cf2_obs_consume", "cf2_obs_rows",
     "cf2_xchg_bind", "cf2_xchg_unique_id", "cf2_xchg_create", "cf2_xchg_destroy", "cf2_xchg_register",
     "cf2_xchg_publish", "cf2_xchg_wait_free", "cf2_xchg_wait", "cf2_xchg_pred_to_host", "cf2_xchg_begin", "cf2_xchg_step", "cf2_xchg_end", "cf2_xchg_env_step", "cf2_xchg_run",
@@ -120,6 +122,15 @@ def load() -> ctypes.CDLL:
     lib.cf2_ng_cg_step.argtypes = [vp] * 4 + [u32, u32, ctypes.c_float, vp, vp, vp]
     lib.cf2_ng_direction.argtypes = [vp] * 6 + [u32, u32, ctypes.c_float, ctypes.c_float, vp, vp, vp]
     lib.cf2_ng_line_search.argtypes = [vp] * 3 + [u32] * 4 + [ctypes.c_float, ctypes.c_float] + [vp] * 5
+    lib.cf2_ppo_partial_doubles.restype = ctypes.c_size_t
+    lib.cf2_ppo_partial_doubles.argtypes = [u32]
+    lib.cf2_ppo_policy_partial.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, u32, vp, vp, ctypes.c_float,
+                                           vp, vp, vp, ctypes.c_int, vp, vp, vp, vp]
+    lib.cf2_ppo_value_partial.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, ctypes.c_int, vp, vp, vp, vp]
+    lib.cf2_ppo_fisher_partial.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp]
+    lib.cf2_ppo_reduce.argtypes = [vp, u32, u32, ctypes.c_int, vp, vp, vp, vp]
+    lib.cf2_column_moments_partial.argtypes = [vp, ctypes.c_uint64, u32, vp, vp, vp]
+    lib.cf2_moments_combine.argtypes = [vp, u32, u32, vp, vp]
     lib.cf2_hbm_probe.argtypes =[vp, vp, ctypes.c_size_t, ctypes.c_int, vp]
     lib.cf2_obs_packed_words.restype = ctypes.c_size_t
     lib.cf2_obs_packed_words.argtypes = [u32, u32, u32]
@@ -151,7 +162,7 @@ def load() -> ctypes.CDLL:
         if name not in ("cf2_abi_version", "cf2_config_sizeof", "cf2_status_string", "cf2_last_hip_error",
                         "cf2_policy_weights_count", "cf2_policy_packed_count", "cf2_obs_packed_words",
                         "cf2_xchg_send_words", "cf2_xchg_recv_words", "cf2_episode_stats_scratch_bytes",
-                        "cf2_column_moments_scratch_bytes", "cf2_ppo_scratch_bytes"):
+                        "cf2_column_moments_scratch_bytes", "cf2_ppo_scratch_bytes", "cf2_ppo_partial_doubles"):
             getattr(lib, name).restype = ctypes.c_int
     if lib.cf2_config_sizeof() != ctypes.sizeof(CF2Config):
         raise CF2Error(f"cf2_config size mismatch: C {lib.cf2_config_sizeof()} vs Python {ctypes.sizeof(CF2Config)}")

@@ -5,8 +5,11 @@ global env ids [offset, offset + count) and every random draw is keyed by the gl
 (Philox counter = (block, rng counter, global id, tag)), which makes each env's trajectory
 independent of the number of ranks.  The only exchange is optional: gathering the per-rank
 observation slabs for a policy that lives elsewhere (RCCL all-gather over xGMI on GPUs, gloo on
-CPU).  The reference's MPI gradient all-reduce (utils/mpi_tools.py) belongs to its learner and
-stays out of scope.
+CPU).  The learner's averages over ranks (the reference's utils/mpi_tools.py: mpi_avg_grads,
+mpi_statistics_scalar, mpi_avg) go through ``RankReducer``: one all-gather of a small fp64 block per
+gradient, evaluation, Fisher-vector or moments call, reduced on every rank by cf2_ppo_reduce /
+cf2_moments_combine in rank order, so all ranks hold the same bits (cf2sim.ppo's updaters take
+``group=``).
 
 ``launch_plan`` / ``run_ranks`` start one process per GPU when no launcher (torchrun) did, and
 ``PipelinedObsGather`` overlaps the per-step observation all-gather with the next env-step.
@@ -1078,3 +1081,70 @@ def gather_rows(x, group=None, sizes=None, out=None):
     parts = [torch.empty_like(pad) for _ in range(world)]
     dist.all_gather(parts, pad, group=group)
     return torch.cat([p[:s] for p, s in zip(parts, sizes)], dim=0)
+
+
+class RankReducer:
+    """The all-gather of the data-parallel updates (cf2sim.ppo, ``update_running_statistics``): every
+    rank contributes one fp64 block per call and receives all of them as ``[world, P]`` in rank order;
+    the native reduce (cf2_ppo_reduce, cf2_moments_combine) then computes the same bits on every rank.
+
+    nccl: ``all_gather_into_tensor`` on the current stream, nothing synchronises with the host.  gloo
+    (the rehearsal and test path, also for ranks that share one GPU): a block on the GPU is staged
+    through the host, as ``gather_rows`` does, which synchronises this rank's stream on every call; it
+    is no performance path.  ``group=None``, or a group of one rank, runs no collective: ``gather``
+    returns a view of its input.  ``force=True`` makes the updaters take the partial -> gather ->
+    reduce route at world 1 too (the cost of the second merge level without any link).
+    ``dist.group.WORLD`` names the default group."""
+
+    def __init__(self, group=None, force: bool = False):
+        self.group = group
+        if group is None:
+            self.world, self.rank, self.nccl = 1, 0, False
+        else:
+            import torch.distributed as dist
+            self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
+            self.nccl = dist.get_backend(group) == "nccl"
+        self.active = self.world > 1 or bool(force)
+        self._out = {}
+
+    @classmethod
+    def of(cls, group):
+        """``group`` itself if it is a RankReducer already, else one over it."""
+        return group if isinstance(group, cls) else cls(group)
+
+    def gather(self, block):
+        """[world, P] from this rank's contiguous 1-d block of P words (the same P on every rank).  The
+        result is a buffer of this object, valid until the next gather of the same size."""
+        import torch
+        import torch.distributed as dist
+        if block.dim() != 1 or not block.is_contiguous():
+            raise ValueError("RankReducer.gather needs a contiguous 1-d block")
+        if self.world == 1:
+            return block.view(1, -1)
+        key = (block.numel(), block.dtype, str(block.device))
+        out = self._out.get(key)
+        if out is None:
+            out = self._out[key] = torch.empty(self.world, block.numel(), dtype=block.dtype, device=block.device)
+        if self.nccl:
+            dist.all_gather_into_tensor(out, block, group=self.group)
+        elif block.is_cuda:
+            host = torch.empty(self.world, block.numel(), dtype=block.dtype)
+            dist.all_gather(list(host.unbind(0)), block.cpu(), group=self.group)
+            out.copy_(host)
+        else:
+            dist.all_gather(list(out.unbind(0)), block, group=self.group)
+        return out
+
+    def sum(self, t):
+        """Sum a tensor over the ranks in place (``all_reduce``; the torch paths of the updaters).
+        gloo with a GPU tensor, and nccl with a host tensor, stage through the other side."""
+        import torch.distributed as dist
+        if self.world == 1:
+            return t
+        if t.is_cuda != self.nccl:           # gloo moves host memory, nccl device memory
+            import torch
+            h = t.cpu() if t.is_cuda else t.to(torch.device("cuda", torch.cuda.current_device()))
+            dist.all_reduce(h, group=self.group)
+            return t.copy_(h)
+        dist.all_reduce(t, group=self.group)
+        return t

@@ -6,7 +6,10 @@ cf2_ppo_value_grad) and a torch optimiser on the module's parameters (``PPOUpdat
 optimiser and the KL stop on the device too (``ResidentPPOUpdater``: cf2_adam_step of
 csrc/cf2sim_optim.hip on the flat weight block, cf2_ppo_policy_grad_gated).  The second half of the
 module is the reference's TRPO and NPG updates (``NaturalGradientUpdater``: cf2_ppo_fisher_vec and the
-solver kernels of csrc/cf2sim_natgrad.hip); its header comment restates their rules.
+solver kernels of csrc/cf2sim_natgrad.hip); its header comment restates their rules.  All three
+updaters take ``group=``: the ranks of a process group each hold a shard of the rows and update in
+lock step from all of them (the reference's ``mpi_avg_grads``; the rank-partial calls, cf2_ppo_reduce
+and cf2_moments_combine of csrc/cf2sim_reduce.hip).
 
 Reference behaviour restated (paths relative to phoenix_drone_simulation/algs/):
 
@@ -248,6 +251,253 @@ class DeviceAdam:
         self.step_count.copy_(sd["step"])
 
 
+# ---------------------------------------------------------------------------------------------------
+# Data-parallel updates: every gradient, evaluation and Fisher-vector call in two levels.  A rank
+# writes a rank-partial block (cf2_ppo_*_partial: its block partials summed in fp64, not divided),
+# ``RankReducer.gather`` all-gathers the blocks, and cf2_ppo_reduce sums them in rank order, divides
+# by the ranks' row count and rounds once -- on every rank, from the same bits, in the same order.
+# grad, summary and with them the KL stop, the CG scalars and the line-search decision are therefore
+# the same everywhere, and the weights stay in lock step with no broadcast.
+# ---------------------------------------------------------------------------------------------------
+def _check_partial(lib, flat, obs, n, idx, m, partial, scratch):
+    from .vec_env import _check_buf
+    dev, f32 = flat.device, torch.float32
+    if dev.type != "cuda":
+        raise ValueError("the PPO gradient kernels need buffers on the GPU")
+    d = obs.shape[-1] if obs.dim() == 2 else -1
+    if d not in (34, 42):
+        raise ValueError(f"obs must be [n, 34] or [n, 42], got {tuple(obs.shape)}")
+    _check_buf(flat, "flat", (lib.cf2_policy_weights_count(d),), f32, dev)
+    _check_buf(obs, "obs", (n, d), f32, dev, align=8)
+    if idx is not None:
+        _check_buf(idx, "idx", (m,), torch.int32, dev)
+    elif m > n:
+        raise ValueError(f"m = {m} rows of n = {n} need idx")
+    if partial is None:
+        raise ValueError("partial is required")
+    _check_buf(partial, "partial", (lib.cf2_ppo_partial_doubles(d),), torch.float64, dev, align=8)
+    need = lib.cf2_ppo_scratch_bytes(m, d)
+    if scratch is None or not isinstance(scratch, torch.Tensor) or scratch.device != dev or not scratch.is_contiguous() \
+            or scratch.data_ptr() % 8 or scratch.numel() * scratch.element_size() < need:
+        raise ValueError(f"scratch must be a contiguous 8-byte aligned tensor of at least {need} bytes on {dev}")
+    return d, dev
+
+
+def policy_partial_device(flat, obs, act, logp_old, adv, clip_ratio: float, partial, scratch, with_grad: bool = True,
+                          idx=None, m: int | None = None, adv_moments=None, moments_count=None, mu_old=None, mu_out=None,
+                          logp_out=None, ctrl=None):
+    """cf2_ppo_policy_partial on torch buffers: ``policy_grad_device`` ending in a rank-partial block
+    (float64 [cf2_ppo_partial_doubles(obs_dim)]) instead of grad and summary.  moments_count: float64
+    [1] on the device, the rows ``adv_moments`` was taken over (all ranks').  m = 0 is legal."""
+    from . import _native
+    from .vec_env import _check_buf
+    lib = _native.load()
+    n = obs.shape[0]
+    m = int(m) if m is not None else (idx.shape[0] if idx is not None else n)
+    d, dev = _check_partial(lib, flat, obs, n, idx, m, partial, scratch)
+    f32 = torch.float32
+    _check_buf(act, "act", (n, 4), f32, dev, align=16)
+    _check_buf(logp_old, "logp_old", (n,), f32, dev)
+    _check_buf(adv, "adv", (n,), f32, dev)
+    _check_buf(adv_moments, "adv_moments", (2,), torch.float64, dev, align=8)
+    _check_buf(moments_count, "moments_count", (1,), torch.float64, dev, align=8)
+    if adv_moments is not None and moments_count is None:
+        raise ValueError("adv_moments needs moments_count, the rows they were taken over")
+    _check_buf(mu_old, "mu_old", (n, 4), f32, dev)
+    _check_buf(mu_out, "mu_out", (m, 4), f32, dev)
+    _check_buf(logp_out, "logp_out", (m,), f32, dev)
+    _check_buf(ctrl, "ctrl", (4,), torch.int32, dev)
+    p = _native.ptr
+    _native.check(lib.cf2_ppo_policy_partial(
+        p(flat), d, p(obs), p(act), p(logp_old), p(adv), n, p(idx), m, p(adv_moments), p(moments_count), float(clip_ratio),
+        p(mu_old), p(mu_out), p(logp_out), int(bool(with_grad)), p(partial), p(scratch), p(ctrl),
+        torch.cuda.current_stream(dev).cuda_stream), "cf2_ppo_policy_partial")
+    return partial
+
+
+def value_partial_device(flat, obs, target, partial, scratch, with_grad: bool = True, idx=None, m: int | None = None,
+                         val_out=None, ctrl=None):
+    """cf2_ppo_value_partial on torch buffers; arguments as ``policy_partial_device``."""
+    from . import _native
+    from .vec_env import _check_buf
+    lib = _native.load()
+    n = obs.shape[0]
+    m = int(m) if m is not None else (idx.shape[0] if idx is not None else n)
+    d, dev = _check_partial(lib, flat, obs, n, idx, m, partial, scratch)
+    _check_buf(target, "target", (n,), torch.float32, dev)
+    _check_buf(val_out, "val_out", (m,), torch.float32, dev)
+    _check_buf(ctrl, "ctrl", (4,), torch.int32, dev)
+    p = _native.ptr
+    _native.check(lib.cf2_ppo_value_partial(
+        p(flat), d, p(obs), p(target), n, p(idx), m, p(val_out), int(bool(with_grad)), p(partial), p(scratch), p(ctrl),
+        torch.cuda.current_stream(dev).cuda_stream), "cf2_ppo_value_partial")
+    return partial
+
+
+def fisher_partial_device(flat, obs, vec, partial, scratch, idx=None, m: int | None = None, ctrl=None):
+    """cf2_ppo_fisher_partial on torch buffers: ``fisher_vec_device`` ending in a rank-partial block."""
+    from . import _native
+    from .vec_env import _check_buf
+    lib = _native.load()
+    n = obs.shape[0]
+    m = int(m) if m is not None else (idx.shape[0] if idx is not None else n)
+    if vec is None:
+        raise ValueError("vec is required")
+    d, dev = _check_partial(lib, flat, obs, n, idx, m, partial, scratch)
+    _check_buf(vec, "vec", (flat.numel(),), torch.float32, dev)
+    _check_buf(ctrl, "ctrl", (4,), torch.int32, dev)
+    p = _native.ptr
+    _native.check(lib.cf2_ppo_fisher_partial(p(flat), d, p(obs), n, p(idx), m, p(vec), p(partial), p(scratch), p(ctrl),
+                                             torch.cuda.current_stream(dev).cuda_stream), "cf2_ppo_fisher_partial")
+    return partial
+
+
+def ppo_reduce_device(blocks, obs_dim: int, which: str, summary, grad=None, ctrl=None):
+    """cf2_ppo_reduce on torch buffers: blocks float64 [world, cf2_ppo_partial_doubles(obs_dim)] in rank
+    order -> the ``which`` ("pi" or "v") slice of the flat block ``grad`` (None: the summary only) and
+    ``summary``, exactly the words the single-rank call writes.  Nothing synchronises."""
+    from . import _native
+    from .vec_env import _check_buf
+    lib = _native.load()
+    if which not in ("pi", "v"):
+        raise ValueError(f"which must be 'pi' or 'v', got {which!r}")
+    P = lib.cf2_ppo_partial_doubles(int(obs_dim))
+    if P == 0:
+        raise ValueError(f"obs_dim must be 34 or 42, got {obs_dim}")
+    if not isinstance(blocks, torch.Tensor) or blocks.dim() != 2 or blocks.shape[0] < 1 or blocks.device.type != "cuda":
+        raise ValueError("blocks must be [world, P] on the GPU")
+    dev, world = blocks.device, blocks.shape[0]
+    _check_buf(blocks, "blocks", (world, P), torch.float64, dev, align=8)
+    if summary is None:
+        raise ValueError("summary is required")
+    _check_buf(summary, "summary", (8,), torch.float64, dev, align=8)
+    _check_buf(grad, "grad", (lib.cf2_policy_weights_count(int(obs_dim)),), torch.float32, dev)
+    _check_buf(ctrl, "ctrl", (4,), torch.int32, dev)
+    p = _native.ptr
+    _native.check(lib.cf2_ppo_reduce(p(blocks), world, int(obs_dim), int(which == "v"), p(grad), p(summary), p(ctrl),
+                                     torch.cuda.current_stream(dev).cuda_stream), "cf2_ppo_reduce")
+    return summary
+
+
+def moments_partial_device(x, block, scratch):
+    """cf2_column_moments_partial on torch buffers: x float32 [rows, D] (or [rows]: D = 1) -> block
+    float64 [1 + 2 D] = {rows, mean[D], M2[D]}; rows = 0 writes a zeroed block."""
+    from . import _native
+    from .vec_env import _check_buf
+    lib = _native.load()
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device.type != "cuda" or not x.is_contiguous() \
+            or x.dim() not in (1, 2):
+        raise ValueError("x must be a contiguous float32 [rows] or [rows, D] tensor on the GPU")
+    rows, d = x.shape[0], (1 if x.dim() == 1 else x.shape[1])
+    if block is None:
+        raise ValueError("block is required")
+    _check_buf(block, "block", (1 + 2 * d,), torch.float64, x.device, align=8)
+    need = lib.cf2_column_moments_scratch_bytes(rows, d)
+    if rows and (scratch is None or scratch.device != x.device or scratch.data_ptr() % 8
+                 or scratch.numel() * scratch.element_size() < need):
+        raise ValueError(f"scratch needs {need} bytes, 8-byte aligned, on {x.device}")
+    _native.check(lib.cf2_column_moments_partial(x.data_ptr() if rows else None, rows, d, block.data_ptr(),
+                                                 _native.ptr(scratch), torch.cuda.current_stream(x.device).cuda_stream),
+                  "cf2_column_moments_partial")
+    return block
+
+
+def moments_combine_device(blocks, out):
+    """cf2_moments_combine on torch buffers: blocks float64 [world, 1 + 2 D] in rank order -> out
+    float64 [1 + 2 D] = {count, mean[D], M2[D]} of all ranks' rows."""
+    from . import _native
+    from .vec_env import _check_buf
+    if not isinstance(blocks, torch.Tensor) or blocks.dim() != 2 or blocks.shape[0] < 1 or blocks.shape[1] < 3 \
+            or blocks.shape[1] % 2 == 0 or blocks.device.type != "cuda":
+        raise ValueError("blocks must be [world, 1 + 2 D] on the GPU")
+    dev, world, words = blocks.device, blocks.shape[0], blocks.shape[1]
+    _check_buf(blocks, "blocks", (world, words), torch.float64, dev, align=8)
+    if out is None:
+        raise ValueError("out is required")
+    _check_buf(out, "out", (words,), torch.float64, dev, align=8)
+    _native.check(_native.load().cf2_moments_combine(blocks.data_ptr(), world, (words - 1) // 2, out.data_ptr(),
+                                                     torch.cuda.current_stream(dev).cuda_stream), "cf2_moments_combine")
+    return out
+
+
+class _RankCalls:
+    """The device calls of an updater with a ``RankReducer``: the signatures of ``policy_grad_device``,
+    ``value_grad_device`` and ``fisher_vec_device``, each as partial -> all-gather -> reduce, plus the
+    advantage moments of all ranks' rows (``mom``: {count, mean, M2} on the device)."""
+
+    def __init__(self, reducer, d: int, dev):
+        from . import _native
+        self.reducer, self.d = reducer, d
+        f64 = torch.float64
+        self.partial = torch.zeros(_native.load().cf2_ppo_partial_doubles(d), dtype=f64, device=dev)
+        self.mom_block = torch.zeros(3, dtype=f64, device=dev)
+        self.mom = torch.zeros(3, dtype=f64, device=dev)
+
+    def moments(self, adv, scratch):
+        moments_partial_device(adv, self.mom_block, scratch)
+        moments_combine_device(self.reducer.gather(self.mom_block), self.mom)
+
+    def policy(self, flat, obs, act, logp_old, adv, clip_ratio, summary, scratch, grad=None, mu_old=None, mu_out=None,
+               ctrl=None):
+        policy_partial_device(flat, obs, act, logp_old, adv, clip_ratio, self.partial, scratch, with_grad=grad is not None,
+                              adv_moments=self.mom[1:], moments_count=self.mom[:1], mu_old=mu_old, mu_out=mu_out, ctrl=ctrl)
+        return ppo_reduce_device(self.reducer.gather(self.partial), self.d, "pi", summary, grad=grad, ctrl=ctrl)
+
+    def value(self, flat, obs, target, summary, scratch, grad=None, idx=None):
+        value_partial_device(flat, obs, target, self.partial, scratch, with_grad=grad is not None, idx=idx)
+        return ppo_reduce_device(self.reducer.gather(self.partial), self.d, "v", summary, grad=grad)
+
+    def fisher(self, flat, obs, vec, out, summary, scratch, idx=None):
+        fisher_partial_device(flat, obs, vec, self.partial, scratch, idx=idx)
+        return ppo_reduce_device(self.reducer.gather(self.partial), self.d, "pi", summary, grad=out)
+
+
+def _rank_mean_grads(reducer, params, count: int) -> float:
+    """The torch paths' ``mpi_avg_grads``: ``.grad`` of params holds the gradient of a *sum* over this
+    rank's ``count`` rows; afterwards it holds the gradient of the mean over all ranks' rows (each
+    rank's mean weighted by its row count, so ragged shards give the global mean).  One all_reduce;
+    returns the ranks' row count."""
+    params = list(params)
+    flat = torch.cat([p.grad.reshape(-1).double() for p in params] + [torch.tensor([float(count)], dtype=torch.float64,
+                                                                                     device=params[0].device)])
+    reducer.sum(flat)
+    total = float(flat[-1])
+    off = 0
+    for p in params:
+        p.grad.copy_((flat[off:off + p.numel()] / max(total, 1.0)).view_as(p.grad))     # no rows anywhere: zeros
+        off += p.numel()
+    return total
+
+
+def _rank_sums(reducer, *values) -> list:
+    """Sums over the ranks of a few host scalars, in fp64 (one all_reduce)."""
+    t = torch.tensor([float(v) for v in values], dtype=torch.float64)
+    reducer.sum(t)
+    return t.tolist()
+
+
+@torch.no_grad()
+def _rank_standardized(reducer, adv, dtype):
+    """(adv - mean) / (std + 1e-8) with the moments of all ranks' advantages, in fp64 (two all_reduces:
+    the mean, then the squares about it); also returns the ranks' row count."""
+    a64 = adv.double()
+    N, total = _rank_sums(reducer, a64.numel(), a64.sum())
+    mean = total / N
+    std = (_rank_sums(reducer, ((a64 - mean) ** 2).sum())[0] / N) ** 0.5
+    return ((a64 - mean) / (std + 1e-8)).to(dtype), N
+
+
+def _rank_value_step(reducer, ac, optimizer, params, obs, target, max_grad_norm: float = 0.0) -> None:
+    """One value mini-batch step across ranks: the mean squared error over all ranks' rows of the
+    piece (this rank's may be empty)."""
+    optimizer.zero_grad()
+    ((ac.v_net(_standardized(ac, obs)).squeeze(-1) - target) ** 2).sum().backward()
+    _rank_mean_grads(reducer, params, obs.shape[0])
+    if max_grad_norm > 0.0:
+        nn.utils.clip_grad_norm_(params, max_grad_norm)
+    optimizer.step()
+
+
 class PPOUpdater:
     """The reference's ``update`` on a ``Rollout``: advantage moments, ``train_pi_iterations`` full-batch
     policy iterations (gradient -> ``pi_optimizer.step()`` -> KL check, stop once the exact KL to the
@@ -260,11 +510,21 @@ class PPOUpdater:
     ``policy_loss_torch`` / ``value_loss_torch`` and autograd, on any device.  ``generator``: the
     torch.Generator of the value passes' permutations (default: the global one of the rollout's
     device).  Scratch, gradient and index buffers are allocated once and re-used while the rollout's
-    shape stays the same."""
+    shape stays the same.
+
+    ``group``: a torch.distributed process group (or a ``cf2sim.dist.RankReducer``) whose ranks each
+    hold a shard of the rows and an identical copy of the module and the optimisers.  Every loss,
+    gradient and logged value is then the mean over all ranks' rows (the reference's ``mpi_avg_grads``
+    / ``mpi_avg``): on the device path through the rank-partial calls and cf2_ppo_reduce, on the torch
+    path through ``all_reduce`` with each rank's mean weighted by its row count.  Every rank permutes
+    its own rows with its own generator and mini-batch j of all ranks is one step, as in the
+    reference; a pass has ``num_mini_batches`` steps on every rank, some of a rank's pieces empty if it
+    has fewer rows.  All ranks compute the same bits, so the modules stay equal without a broadcast.
+    None (the default): one rank, today's calls."""
 
     def __init__(self, ac: MLPActorCritic, pi_optimizer, v_optimizer, clip_ratio: float, target_kl: float,
                  train_pi_iterations: int = 80, train_v_iterations: int = 5, num_mini_batches: int = 16,
-                 fused=None, device: bool = True, generator: torch.Generator | None = None):
+                 fused=None, device: bool = True, generator: torch.Generator | None = None, group=None):
         if fused is not None and fused.ac is not ac:
             raise ValueError("fused must wrap the same MLPActorCritic")
         if num_mini_batches < 1:
@@ -274,14 +534,17 @@ class PPOUpdater:
         self.train_pi_iterations, self.train_v_iterations = int(train_pi_iterations), int(train_v_iterations)
         self.num_mini_batches = int(num_mini_batches)
         self.fused, self.device, self.generator = fused, bool(device), generator
+        from .dist import RankReducer
+        self.reducer = RankReducer.of(group)
         self._bufs = None
 
     def value_minibatches(self, n: int, dev) -> list[torch.Tensor]:
         """One value pass: a permutation of the n rows cut into num_mini_batches consecutive pieces
-        (sizes differ by at most one; every row is in exactly one)."""
+        (sizes differ by at most one; every row is in exactly one).  Across ranks every rank cuts
+        num_mini_batches pieces, empty ones included, so that all ranks take the same number of steps."""
         gen_dev = self.generator.device if self.generator is not None else dev
         perm = torch.randperm(n, generator=self.generator, device=gen_dev).to(dev)
-        nb = min(self.num_mini_batches, n)
+        nb = self.num_mini_batches if self.reducer.active else min(self.num_mini_batches, n)
         return [perm[(k * n) // nb:((k + 1) * n) // nb] for k in range(nb)]
 
     def _buffers(self, n: int, d: int, dev):
@@ -299,6 +562,8 @@ class PPOUpdater:
                 "moments": torch.empty(2, dtype=torch.float64, device=dev),
                 "summary": torch.empty(8, dtype=torch.float64, device=dev),
             }
+            if self.reducer.active:
+                self._bufs["calls"] = _RankCalls(self.reducer, d, dev)
         return self._bufs
 
     def update(self, rollout: Rollout) -> dict:
@@ -323,21 +588,28 @@ class PPOUpdater:
         obs, act, logp_old, adv, ret = (t.contiguous() for t in (obs, act, logp_old, adv, ret))
         B = self._buffers(n, d, dev)
         scratch, grad, summary, mu_old, mom = B["scratch"], B["grad"], B["summary"], B["mu_old"], B["moments"]
-        lib = _native.load()
-        _native.check(lib.cf2_column_moments(adv.data_ptr(), n, 1, mom.data_ptr(), scratch.data_ptr(),
-                                             torch.cuda.current_stream(dev).cuda_stream), "cf2_column_moments")
+        if self.reducer.active:
+            R = B["calls"]
+            R.moments(adv, scratch)
+            pol = lambda flat, **kw: R.policy(flat, obs, act, logp_old, adv, c, summary, scratch, **kw)
+            val = lambda flat, **kw: R.value(flat, obs, ret, summary, scratch, **kw)
+        else:
+            lib = _native.load()
+            _native.check(lib.cf2_column_moments(adv.data_ptr(), n, 1, mom.data_ptr(), scratch.data_ptr(),
+                                                 torch.cuda.current_stream(dev).cuda_stream), "cf2_column_moments")
+            pol = lambda flat, **kw: policy_grad_device(flat, obs, act, logp_old, adv, c, summary, scratch, adv_moments=mom,
+                                                        **kw)
+            val = lambda flat, **kw: value_grad_device(flat, obs, ret, summary, scratch, **kw)
         flat = pack_policy_weights(ac)
-        before = policy_grad_device(flat, obs, act, logp_old, adv, c, summary, scratch, adv_moments=mom,
-                                    mu_out=mu_old).clone()
-        before_v = value_grad_device(flat, obs, ret, summary, scratch).clone()
+        before = pol(flat, mu_out=mu_old).clone()
+        before_v = val(flat).clone()
         kl, clip_frac, stop = 0.0, 0.0, 0
         for i in range(self.train_pi_iterations):
-            policy_grad_device(flat, obs, act, logp_old, adv, c, summary, scratch, grad=grad, adv_moments=mom)
+            pol(flat, grad=grad)
             scatter_flat_grad(ac, grad, "pi")
             self.pi_optimizer.step()
             flat = pack_policy_weights(ac)
-            s = policy_grad_device(flat, obs, act, logp_old, adv, c, summary, scratch, adv_moments=mom,
-                                   mu_old=mu_old).tolist()        # the KL check reads the host, as the reference
+            s = pol(flat, mu_old=mu_old).tolist()                 # the KL check reads the host, as the reference
             kl, clip_frac, stop = s[4], s[3], i + 1
             if kl > self.target_kl:
                 break
@@ -345,7 +617,7 @@ class PPOUpdater:
             for mb in self.value_minibatches(n, dev):
                 idx = B["idx"][:mb.shape[0]]
                 idx.copy_(mb)
-                value_grad_device(flat, obs, ret, summary, scratch, grad=grad, idx=idx)
+                val(flat, grad=grad, idx=idx)
                 scatter_flat_grad(ac, grad, "v")
                 self.v_optimizer.step()
                 flat = pack_policy_weights(ac)
@@ -354,6 +626,8 @@ class PPOUpdater:
 
     # ---- torch autograd (the fall-back, and the reference of the tests)
     def _update_torch(self, obs, act, logp_old, adv, ret) -> dict:
+        if self.reducer.active:
+            return self._update_torch_ranks(obs, act, logp_old, adv, ret)
         ac, c = self.ac, self.clip_ratio
         n, dev = obs.shape[0], obs.device
         with torch.no_grad():
@@ -383,6 +657,35 @@ class PPOUpdater:
                 self.v_optimizer.step()
         return {"LossPi": loss_pi, "LossV": loss_v, "KL": kl, "StopIter": stop, "ClipFrac": clip_frac}
 
+    # ---- torch autograd across ranks: sums per rank, one all_reduce, divided by the ranks' rows
+    def _update_torch_ranks(self, obs, act, logp_old, adv, ret) -> dict:
+        ac, c, R = self.ac, self.clip_ratio, self.reducer
+        n, dev = obs.shape[0], obs.device
+        adv, N = _rank_standardized(R, adv, obs.dtype)
+        pi_params, v_params = list(ac.pi_net.parameters()), list(ac.v_net.parameters())
+        with torch.no_grad():
+            t = policy_terms_torch(ac, obs, act, logp_old, adv, c)
+            mu_old = t["mu"]
+            sq = (ac.v_net(_standardized(ac, obs)).squeeze(-1) - ret) ** 2
+            loss_pi, loss_v = (v / N for v in _rank_sums(R, t["rows"].double().sum(), sq.double().sum()))
+        kl, clip_frac, stop = 0.0, 0.0, 0
+        for i in range(self.train_pi_iterations):
+            self.pi_optimizer.zero_grad()
+            policy_terms_torch(ac, obs, act, logp_old, adv, c)["rows"].sum().backward()
+            _rank_mean_grads(R, pi_params, n)
+            self.pi_optimizer.step()
+            with torch.no_grad():
+                t = policy_terms_torch(ac, obs, act, logp_old, adv, c, mu_old=mu_old)
+                kl, clip_frac = (v / N for v in _rank_sums(R, t["kl"].double().sum(),
+                                                           ((t["ratio"] - 1.0).abs() > c).double().sum()))
+            stop = i + 1
+            if kl > self.target_kl:
+                break
+        for _ in range(self.train_v_iterations):
+            for mb in self.value_minibatches(n, dev):
+                _rank_value_step(R, ac, self.v_optimizer, v_params, obs[mb], ret[mb])
+        return {"LossPi": loss_pi, "LossV": loss_v, "KL": kl, "StopIter": stop, "ClipFrac": clip_frac}
+
 
 class ResidentPPOUpdater:
     """``PPOUpdater(device=True)`` with the optimiser and the loop control on the device: the flat
@@ -409,14 +712,22 @@ class ResidentPPOUpdater:
     ``unpack_policy_weights`` and ``fused.sync_from_flat``.  ``update(rollout, read=True)`` reads the
     six results in one transfer at the very end; ``read=False`` returns None without any host
     synchronisation, ``result()`` reads later.  A generator on the rollout's device (or None) keeps
-    the permutations on the device too.  ``max_grad_norm``: None or 0 turns clipping off."""
+    the permutations on the device too.  ``max_grad_norm``: None or 0 turns clipping off.
+
+    ``group``: as ``PPOUpdater``'s.  Each gradient and evaluation launch pair becomes rank partial ->
+    all-gather -> cf2_ppo_reduce, the advantage moments cf2_column_moments_partial -> all-gather ->
+    cf2_moments_combine; the Adam launches then read the same grad and summary on every rank, so the
+    KL stop falls at the same step everywhere.  Over nccl ``read=False`` still returns without a host
+    read; over gloo every all-gather stages through the host (the rehearsal path).  A mini-batch in
+    which no rank has a row (fewer rows in all than ``num_mini_batches``) would step on a stale gradient:
+    keep ``num_mini_batches`` at or below the ranks' row count."""
 
     KEYS = ("LossPi", "LossV", "KL", "ClipFrac", "StopIter", "GradNormPi")
 
     def __init__(self, ac: MLPActorCritic, pi_lr: float, v_lr: float, clip_ratio: float, target_kl: float,
                  train_pi_iterations: int = 80, train_v_iterations: int = 5, num_mini_batches: int = 16,
                  betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float | None = None, fused=None,
-                 generator: torch.Generator | None = None):
+                 generator: torch.Generator | None = None, group=None):
         if fused is not None and fused.ac is not ac:
             raise ValueError("fused must wrap the same MLPActorCritic")
         if num_mini_batches < 1:
@@ -427,6 +738,8 @@ class ResidentPPOUpdater:
         self.clip_ratio, self.target_kl = float(clip_ratio), float(target_kl)
         self.train_pi_iterations, self.train_v_iterations = int(train_pi_iterations), int(train_v_iterations)
         self.num_mini_batches = int(num_mini_batches)
+        from .dist import RankReducer
+        self.reducer = RankReducer.of(group)
         dev = next(ac.parameters()).device
         if dev.type != "cuda":
             raise ValueError("ResidentPPOUpdater needs the module on the GPU")
@@ -473,14 +786,22 @@ class ResidentPPOUpdater:
         B = self._buffers(n, d, dev)
         scratch, grad, mu_old, mom = B["scratch"], B["grad"], B["mu_old"], B["moments"]
         summary0, summary, ctrl = self.summary0, self.summary, self.ctrl
-        lib = _native.load()
-        _native.check(lib.cf2_column_moments(adv.data_ptr(), n, 1, mom.data_ptr(), scratch.data_ptr(),
-                                             torch.cuda.current_stream(dev).cuda_stream), "cf2_column_moments")
+        if self.reducer.active:
+            R = B["calls"]
+            R.moments(adv, scratch)
+            pol = lambda summ, **kw: R.policy(flat, obs, act, logp_old, adv, c, summ, scratch, **kw)
+            val = lambda summ, **kw: R.value(flat, obs, ret, summ, scratch, **kw)
+        else:
+            lib = _native.load()
+            _native.check(lib.cf2_column_moments(adv.data_ptr(), n, 1, mom.data_ptr(), scratch.data_ptr(),
+                                                 torch.cuda.current_stream(dev).cuda_stream), "cf2_column_moments")
+            pol = lambda summ, **kw: policy_grad_device(flat, obs, act, logp_old, adv, c, summ, scratch, adv_moments=mom,
+                                                        **kw)
+            val = lambda summ, **kw: value_grad_device(flat, obs, ret, summ, scratch, **kw)
         flat = pack_policy_weights(ac)
         ctrl.zero_()
         summary.zero_()                   # KL and ClipFrac of an update without a policy step
-        pol = lambda summ, **kw: policy_grad_device(flat, obs, act, logp_old, adv, c, summ, scratch, adv_moments=mom, **kw)
-        value_grad_device(flat, obs, ret, self.summary_v, scratch)
+        val(self.summary_v)
         iters = self.train_pi_iterations
         pol(summary0, mu_out=mu_old, grad=grad if iters > 0 else None)
         if iters > 0:
@@ -493,7 +814,7 @@ class ResidentPPOUpdater:
             for mb in self.value_minibatches(n, dev):
                 idx = B["idx"][:mb.shape[0]]
                 idx.copy_(mb)
-                value_grad_device(flat, obs, ret, self.summary_mb, scratch, grad=grad, idx=idx)
+                val(self.summary_mb, grad=grad, idx=idx)
                 self.v_optimizer.step(flat, grad)
         unpack_policy_weights(ac, flat)
         if self.fused is not None:
@@ -742,8 +1063,12 @@ class NaturalGradientUpdater:
     rejected; ng_state also holds their loss), AcceptanceStep (accepted trial + 1; 0: all rejected; NPG: 1),
     StepFrac, xHx, Alpha, ExpectedImprove, CGResidual (|r| after the last CG step), GradNormPi.
 
-    Single rank: the reference averages the gradient and the Fisher-vector product over MPI ranks
-    (``mpi_avg_grads``); that is out of scope here, as it is for ``ResidentPPOUpdater``."""
+    ``group``: as ``PPOUpdater``'s.  The reference averages the gradient and the Fisher-vector product
+    over ranks (``mpi_avg_grads``): here the G0, evaluation and Fisher-vector calls go rank partial ->
+    all-gather -> cf2_ppo_reduce (every rank takes every ``fvp_stride``-th of its own rows, as every
+    process of the reference does), so ``ng_state`` -- the CG scalars, the step size and the line
+    search's decision -- is the same on every rank.  ``device=False`` averages the same quantities
+    with ``all_reduce``, each rank weighted by its row count."""
 
     KEYS = ("LossPi", "LossV", "KL", "AcceptanceStep", "StepFrac", "xHx", "Alpha", "ExpectedImprove", "CGResidual",
             "GradNormPi")
@@ -752,7 +1077,7 @@ class NaturalGradientUpdater:
                  cg_damping: float = 0.1, fvp_stride: int = 4, line_search_steps: int = 25,
                  line_search_decay: float = 0.8, train_v_iterations: int = 5, num_mini_batches: int = 16,
                  betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float | None = None, fused=None,
-                 generator: torch.Generator | None = None, device: bool = True):
+                 generator: torch.Generator | None = None, device: bool = True, group=None):
         if algorithm not in ("trpo", "npg"):
             raise ValueError(f"algorithm must be 'trpo' or 'npg', got {algorithm!r}")
         if fused is not None and fused.ac is not ac:
@@ -768,6 +1093,8 @@ class NaturalGradientUpdater:
         self.train_v_iterations, self.num_mini_batches = int(train_v_iterations), int(num_mini_batches)
         self.max_grad_norm = 0.0 if max_grad_norm is None else float(max_grad_norm)
         self.device = bool(device)
+        from .dist import RankReducer
+        self.reducer = RankReducer.of(group)
         self._bufs, self._pending, self.flat = None, None, None
         dev = next(ac.parameters()).device
         if self.device:
@@ -831,15 +1158,24 @@ class NaturalGradientUpdater:
             B["fvp_stride"] = self.fvp_stride
         fidx = B["fvp_idx"]
         summary0, summary, ctrl, st, W = self.summary0, self.summary, self.ctrl, self.ng_state, self.work
-        lib = _native.load()
-        _native.check(lib.cf2_column_moments(adv.data_ptr(), n, 1, mom.data_ptr(), scratch.data_ptr(),
-                                             torch.cuda.current_stream(dev).cuda_stream), "cf2_column_moments")
+        if self.reducer.active:
+            R = B["calls"]
+            R.moments(adv, scratch)
+            pol = lambda summ, **kw: R.policy(flat, obs, act, logp_old, adv, inf, summ, scratch, **kw)
+            fvp = lambda vec: R.fisher(flat, obs, vec, W["z"], self.summary_f, scratch, idx=fidx)
+            val = lambda summ, **kw: R.value(flat, obs, ret, summ, scratch, **kw)
+        else:
+            lib = _native.load()
+            _native.check(lib.cf2_column_moments(adv.data_ptr(), n, 1, mom.data_ptr(), scratch.data_ptr(),
+                                                 torch.cuda.current_stream(dev).cuda_stream), "cf2_column_moments")
+            pol = lambda summ, **kw: policy_grad_device(flat, obs, act, logp_old, adv, inf, summ, scratch, adv_moments=mom,
+                                                        **kw)
+            fvp = lambda vec: fisher_vec_device(flat, obs, vec, W["z"], self.summary_f, scratch, idx=fidx)
+            val = lambda summ, **kw: value_grad_device(flat, obs, ret, summ, scratch, **kw)
         flat = pack_policy_weights(ac)
         ctrl.zero_()
         p0, p1 = flat_slice(ac, "pi")
-        pol = lambda summ, **kw: policy_grad_device(flat, obs, act, logp_old, adv, inf, summ, scratch, adv_moments=mom, **kw)
-        fvp = lambda vec: fisher_vec_device(flat, obs, vec, W["z"], self.summary_f, scratch, idx=fidx)
-        value_grad_device(flat, obs, ret, self.summary_v, scratch)
+        val(self.summary_v)
         pol(summary0, mu_out=mu_old, grad=grad)
         ng_cg_init_device(grad, W["b"], W["x"], W["r"], W["p"], p0, p1 - p0, st)
         for _ in range(self.cg_iters):
@@ -862,7 +1198,7 @@ class NaturalGradientUpdater:
             for mb in self.value_minibatches(n, dev):
                 idx = B["idx"][:mb.shape[0]]
                 idx.copy_(mb)
-                value_grad_device(flat, obs, ret, self.summary_mb, scratch, grad=grad, idx=idx)
+                val(self.summary_mb, grad=grad, idx=idx)
                 self.v_optimizer.step(flat, grad)
         unpack_policy_weights(ac, flat)
         if self.fused is not None:
@@ -874,30 +1210,55 @@ class NaturalGradientUpdater:
 
     # ---- torch autograd (the fall-back, and the reference of the tests)
     def _update_torch(self, obs, act, logp_old, adv, ret) -> None:
-        ac, inf, kl_t, damp = self.ac, float("inf"), self.target_kl, self.cg_damping
+        ac, inf, kl_t, damp, R = self.ac, float("inf"), self.target_kl, self.cg_damping, self.reducer
         n, dev = obs.shape[0], obs.device
         params = [p for m in _linears(ac, "pi") for p in (m.weight, m.bias)]
-        with torch.no_grad():
-            a64 = adv.double()
-            mean = a64.mean()
-            std = torch.sqrt(((a64 - mean) ** 2).sum() / n)
-            adv = ((a64 - mean) / (std + 1e-8)).to(obs.dtype)
-            mu_old = policy_terms_torch(ac, obs, act, logp_old, adv, inf)["mu"]
-            loss_v = float(value_loss_torch(ac, obs, ret))
-
-        def evaluate():
-            with torch.no_grad():
-                t = policy_terms_torch(ac, obs, act, logp_old, adv, inf, mu_old=mu_old)
-                return float(t["rows"].double().mean()), float(t["kl"].double().mean())
-
-        rows = policy_terms_torch(ac, obs, act, logp_old, adv, inf)["rows"]
-        g = pi_flat(ac, torch.autograd.grad(rows.mean(), params))
-        loss_before = float(rows.detach().double().mean())
         sub = obs[::self.fvp_stride]
+        if R.active:
+            # sums per rank, one all_reduce each, divided by the ranks' rows
+            adv, N = _rank_standardized(R, adv, obs.dtype)
+            v_params = list(ac.v_net.parameters())
+            with torch.no_grad():
+                mu_old = policy_terms_torch(ac, obs, act, logp_old, adv, inf)["mu"]
+                sq = (ac.v_net(_standardized(ac, obs)).squeeze(-1) - ret) ** 2
+                loss_v = _rank_sums(R, sq.double().sum())[0] / N
+
+            def evaluate():
+                with torch.no_grad():
+                    t = policy_terms_torch(ac, obs, act, logp_old, adv, inf, mu_old=mu_old)
+                    return tuple(v / N for v in _rank_sums(R, t["rows"].double().sum(), t["kl"].double().sum()))
+
+            def rank_mean(vec, count):
+                both = torch.cat([vec.double() * count, torch.tensor([float(count)], dtype=torch.float64, device=vec.device)])
+                R.sum(both)
+                return (both[:-1] / both[-1]).to(vec.dtype)
+
+            rows = policy_terms_torch(ac, obs, act, logp_old, adv, inf)["rows"]
+            g = rank_mean(pi_flat(ac, torch.autograd.grad(rows.mean(), params)), n)
+            loss_before = _rank_sums(R, rows.detach().double().sum())[0] / N
+            fvp = lambda vec: rank_mean(fisher_vec_torch(ac, sub, vec), sub.shape[0])
+        else:
+            with torch.no_grad():
+                a64 = adv.double()
+                mean = a64.mean()
+                std = torch.sqrt(((a64 - mean) ** 2).sum() / n)
+                adv = ((a64 - mean) / (std + 1e-8)).to(obs.dtype)
+                mu_old = policy_terms_torch(ac, obs, act, logp_old, adv, inf)["mu"]
+                loss_v = float(value_loss_torch(ac, obs, ret))
+
+            def evaluate():
+                with torch.no_grad():
+                    t = policy_terms_torch(ac, obs, act, logp_old, adv, inf, mu_old=mu_old)
+                    return float(t["rows"].double().mean()), float(t["kl"].double().mean())
+
+            rows = policy_terms_torch(ac, obs, act, logp_old, adv, inf)["rows"]
+            g = pi_flat(ac, torch.autograd.grad(rows.mean(), params))
+            loss_before = float(rows.detach().double().mean())
+            fvp = lambda vec: fisher_vec_torch(ac, sub, vec)
         st = cg_init_torch(g)
         for _ in range(self.cg_iters):
-            cg_step_torch(st, fisher_vec_torch(ac, sub, st["p"]), damp)
-        direction_torch(st, fisher_vec_torch(ac, sub, st["x"]), damp, kl_t)
+            cg_step_torch(st, fvp(st["p"]), damp)
+        direction_torch(st, fvp(st["x"]), damp, kl_t)
         theta_old = pi_flat(ac).clone()
         set_pi_flat(ac, theta_old + st["step"])
         if self.algorithm == "trpo":
@@ -918,6 +1279,9 @@ class NaturalGradientUpdater:
             after = (kl_j, 1, 1.0)
         for _ in range(self.train_v_iterations):
             for mb in self.value_minibatches(n, dev):
+                if R.active:
+                    _rank_value_step(R, ac, self.v_optimizer, v_params, obs[mb], ret[mb], self.max_grad_norm)
+                    continue
                 self.v_optimizer.zero_grad()
                 value_loss_torch(ac, obs[mb], ret[mb]).backward()
                 if self.max_grad_norm > 0.0:
@@ -931,4 +1295,6 @@ __all__ = ["policy_loss_torch", "policy_terms_torch", "value_loss_torch", "scatt
            "policy_grad_device", "value_grad_device", "adam_step_device", "DeviceAdam", "PPOUpdater",
            "ResidentPPOUpdater", "pi_flat", "pi_unflat", "set_pi_flat", "fisher_vec_torch", "cg_init_torch",
            "cg_step_torch", "direction_torch", "line_search_torch", "fisher_vec_device", "ng_cg_init_device",
-           "ng_cg_step_device", "ng_direction_device", "ng_line_search_device", "NaturalGradientUpdater"]
+           "ng_cg_step_device", "ng_direction_device", "ng_line_search_device", "NaturalGradientUpdater", "policy_partial_device",
+           "value_partial_device", "fisher_partial_device", "ppo_reduce_device", "moments_partial_device",
+           "moments_combine_device"]

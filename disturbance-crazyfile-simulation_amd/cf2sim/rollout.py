@@ -57,8 +57,8 @@ _ACT = {"relu": nn.ReLU, "tanh": nn.Tanh, "identity": nn.Identity}
 
 class OnlineMeanStd(nn.Module):
     """Running mean / standard deviation (utils/online_mean_std.py): the incremental update of
-    Chan et al. over batches, single process (the reference's MPI averages are the identity with
-    one process; across GPUs, batches of every rank can be concatenated before update()).
+    Chan et al. over batches.  ``update`` / ``update_device`` with ``group=`` first combine the ranks'
+    batch moments (the reference's MPI averages), so every rank carries the same statistics.
 
     Provenance: this restates the reference's OnlineMeanStd closely -- same epsilon, same clip
     bound 10, the same n_A / n_AB / delta / mean / M2 update in the same order -- because the
@@ -91,7 +91,10 @@ class OnlineMeanStd(nn.Module):
         return self._std_host
 
     @torch.no_grad()
-    def update(self, x: torch.Tensor) -> None:
+    def update(self, x: torch.Tensor, group=None) -> None:
+        """One batch.  ``group`` (a process group or a ``cf2sim.dist.RankReducer``): the batch is the
+        ranks' batches together -- their moments are combined by ``rank_moments_torch`` and go through
+        ``update_from_moments``, so every rank ends with the same bits."""
         x = torch.as_tensor(x, dtype=torch.float32, device=self.mean.device)
         if self.shape[0] == 1:
             if x.dim() != 1:
@@ -99,6 +102,10 @@ class OnlineMeanStd(nn.Module):
             x = x.view(-1, 1)
         elif x.dim() != 2 or x.shape[1] != self.shape[0]:
             raise ValueError(f"expected [B, {self.shape[0]}], got {tuple(x.shape)}")
+        from .dist import RankReducer
+        if RankReducer.of(group).active:
+            self.update_from_moments(*rank_moments_torch(x, group))
+            return
         n_b = x.shape[0]
         n_a = self.count.clone()
         n_ab = self.count + n_b
@@ -115,15 +122,20 @@ class OnlineMeanStd(nn.Module):
         """``update`` from a batch's moments instead of its rows: n_b rows with column means mean_b
         and M2_b = sum (x - mean_b)^2.  Same arithmetic, including update's batch variance about the
         *new* mean (the part golden_f3.npz pins), which from moments is
-        (M2_b + n_b (mean_b - mean_new)^2) / n_b.  Evaluated in fp64 (count read into fp64; the fp32
+        (M2_b + n_b (mean_b - mean_new)^2) / n_b.  n_b may be a one-element float64 tensor on the
+        statistics' device (the ranks' row count from cf2_moments_combine; it is not checked, so that
+        nothing waits for it).  Evaluated in fp64 (count read into fp64; the fp32
         count buffer alone would stop counting single rows at 2^24) and rounded once into the fp32
         buffers; no host synchronisation."""
         dev = self.mean.device
         mean_b = torch.as_tensor(mean_b, dtype=torch.float64, device=dev).reshape(self.shape)
         m2_b = torch.as_tensor(m2_b, dtype=torch.float64, device=dev).reshape(self.shape)
-        n_b = int(n_b)
-        if n_b <= 0:
-            raise ValueError(f"a batch has at least one row, got {n_b}")
+        if isinstance(n_b, torch.Tensor):
+            n_b = n_b.to(device=dev, dtype=torch.float64).reshape(())
+        else:
+            n_b = int(n_b)
+            if n_b <= 0:
+                raise ValueError(f"a batch has at least one row, got {n_b}")
         n_a = self.count.double()
         n_ab = n_a + n_b
         mean_a = self.mean.double()
@@ -136,10 +148,13 @@ class OnlineMeanStd(nn.Module):
         self.std.copy_(torch.sqrt(m2_ab / n_ab))
 
     @torch.no_grad()
-    def update_device(self, x: torch.Tensor) -> None:
+    def update_device(self, x: torch.Tensor, group=None) -> None:
         """``update(x)`` for a float32 batch on the GPU in one pass over x: cf2_column_moments
         (fp64 column means and M2, csrc/cf2sim_stats.hip), then ``update_from_moments``.  x is
-        [B, D] (or [B] for shape (1,) statistics), contiguous; nothing synchronises with the host."""
+        [B, D] (or [B] for shape (1,) statistics), contiguous; nothing synchronises with the host.
+        ``group``: the ranks' moments blocks (cf2_column_moments_partial) are all-gathered and folded
+        in rank order by cf2_moments_combine first, the same bits on every rank; a rank may have no
+        row.  Over gloo the all-gather stages through the host."""
         from . import _native
         dev = self.mean.device
         d = self.shape[0]
@@ -148,6 +163,23 @@ class OnlineMeanStd(nn.Module):
         if (x.dim() != 1) if d == 1 else (x.dim() != 2 or x.shape[1] != d):
             raise ValueError(f"expected {'[B]' if d == 1 else f'[B, {d}]'}, got {tuple(x.shape)}")
         rows = x.shape[0]
+        from .dist import RankReducer
+        reducer = RankReducer.of(group)
+        if reducer.active:
+            from .ppo import moments_combine_device, moments_partial_device
+            lib = _native.load()
+            need = lib.cf2_column_moments_scratch_bytes(max(rows, 1), d)
+            buf = getattr(self, "_rank_moments_buf", None)
+            if buf is None or buf[0].device != dev or buf[0].numel() * 8 < need:
+                buf = (torch.empty((need + 7) // 8, dtype=torch.float64, device=dev),
+                       torch.empty(1 + 2 * d, dtype=torch.float64, device=dev),
+                       torch.empty(1 + 2 * d, dtype=torch.float64, device=dev))
+                self._rank_moments_buf = buf
+            scratch, block, out = buf
+            moments_partial_device(x, block, scratch)
+            moments_combine_device(reducer.gather(block), out)
+            self.update_from_moments(out[:1], out[1:1 + d], out[1 + d:])
+            return
         if rows == 0:
             raise ValueError("a batch has at least one row, got 0")
         lib = _native.load()
@@ -227,19 +259,53 @@ class MLPActorCritic(nn.Module):
         return torch.distributions.Normal(mu, self.log_std.exp()).log_prob(act).sum(-1)
 
 
+@torch.no_grad()
+def rank_moments_torch(x: torch.Tensor, group) -> tuple:
+    """(count, mean[D], M2[D]) of the ranks' [B_r, D] batches together, in fp64: each rank's two-pass
+    moments, all-gathered (``RankReducer.gather``) and folded left in rank order with the update of
+    Chan et al., batches of no rows skipped -- cf2_moments_combine's arithmetic in torch, for the path
+    that runs without a GPU.  Every rank gets the same bits.  count is a Python int."""
+    from .dist import RankReducer
+    x64 = x.double()
+    rows, d = x64.shape
+    mean = x64.mean(dim=0) if rows else torch.zeros(d, dtype=torch.float64, device=x.device)
+    m2 = ((x64 - mean) ** 2).sum(dim=0)
+    block = torch.cat([torch.tensor([float(rows)], dtype=torch.float64, device=x.device), mean, m2])
+    blocks = RankReducer.of(group).gather(block).cpu()
+    n, mean, m2 = 0.0, None, None
+    for b in blocks:
+        bn = float(b[0])
+        if not bn > 0.0:
+            continue
+        if n == 0.0:
+            n, mean, m2 = bn, b[1:1 + d].clone(), b[1 + d:].clone()
+            continue
+        nab, delta = n + bn, b[1:1 + d] - mean
+        mean = mean + delta * (bn / nab)
+        m2 = m2 + b[1 + d:] + delta * delta * (n * bn / nab)
+        n = nab
+    if n == 0.0:
+        raise ValueError("a batch has at least one row on some rank")
+    return int(n), mean, m2
+
+
 def update_running_statistics(ac: MLPActorCritic, rollout: "Rollout", fused: "FusedActorCritic | None" = None,
-                              device: bool = False):
+                              device: bool = False, group=None):
     """IWPGAlgorithm.update_running_statistics (iwpg.py:412-420) on a whole batched rollout: the raw
     observations update the observation statistics, the discounted returns the return statistics.
     A FusedActorCritic over `ac` is re-synced (its weight block carries the standardisation).
     device=True: both updates read the rollout once through cf2_column_moments
-    (``OnlineMeanStd.update_device``) instead of torch's passes over it."""
+    (``OnlineMeanStd.update_device``) instead of torch's passes over it.
+    group: a process group (or ``cf2sim.dist.RankReducer``) whose ranks each hold a shard of the envs:
+    both updates are from the batch moments of all ranks' rows, so every rank carries the same
+    ``obs_oms`` / ``ret_oms`` (the reference's MPI-averaged statistics)."""
+    kw = {} if group is None else {"group": group}
     if ac.obs_oms is not None:
         upd = ac.obs_oms.update_device if device else ac.obs_oms.update
-        upd(rollout.obs.reshape(-1, rollout.obs.shape[-1]))
+        upd(rollout.obs.reshape(-1, rollout.obs.shape[-1]), **kw)
     if ac.ret_oms is not None:
         upd = ac.ret_oms.update_device if device else ac.ret_oms.update
-        upd(rollout.discounted_ret.reshape(-1))
+        upd(rollout.discounted_ret.reshape(-1), **kw)
     if fused is not None:
         fused.sync()
 

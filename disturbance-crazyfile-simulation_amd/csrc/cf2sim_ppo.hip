@@ -29,7 +29,9 @@
 // Reduction: the four waves of a block add their accumulators into LDS in wave order, the block
 // writes one partial gradient and one partial summary to scratch, and ppo_merge_kernel sums the
 // partials in block-index order in fp64, divides by m and rounds once.  No atomics; the geometry
-// depends on m only, so the same input gives the same bits.
+// depends on m only, so the same input gives the same bits.  The rank-partial calls of the
+// data-parallel updates end in ppo_partial_merge_kernel instead: the same sums, not divided and not
+// rounded, as one block of doubles that cf2_ppo_reduce (cf2sim_reduce.hip) merges across ranks.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/cf2sim.h"
@@ -535,6 +537,44 @@ __global__ void __launch_bounds__(256) ppo_merge_kernel(const float* __restrict_
     }
 }
 
+// Block partials -> one rank-partial block of doubles (data-parallel updates; cf2_ppo_reduce of
+// cf2sim_reduce.hip is the second level): out[0] = m, out[1..7] = the fp64 sums of the summary slots,
+// out[8 + p] = the fp64 sum of gradient word p, all in block-index order as ppo_merge_kernel sums
+// them, not divided and not rounded.  with_grad == 0, and the words past npar up to `words` (the
+// block's fixed size less the head): 0.  blocks == 0 (m == 0): a zeroed block.  gate: as PpoArgs::gate.
+__global__ void __launch_bounds__(256) ppo_partial_merge_kernel(const float* __restrict__ part_grad,
+                                                                const double* __restrict__ part_sum, uint32_t blocks,
+                                                                uint32_t npar, uint32_t words, uint32_t m, int with_grad,
+                                                                double* __restrict__ out,
+                                                                const uint32_t* __restrict__ gate) {
+    if (gate && *gate != 0u) return;
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p < words) {
+        double acc = 0.0;
+        if (with_grad && p < npar) {
+#pragma unroll 8
+            for (uint32_t b = 0; b < blocks; ++b) acc += (double)part_grad[(size_t)b * npar + p];
+        }
+        out[PPO_SUM + p] = acc;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < PPO_SUM) {
+        const uint32_t k = threadIdx.x;
+        double acc = 0.0;
+        for (uint32_t b = 0; b < blocks; ++b) acc += part_sum[(size_t)b * PPO_SUM + k];
+        out[k] = k == 0 ? (double)m : acc;
+    }
+}
+
+// {mean, M2} taken over *count rows -> {mean, M2 rows / *count}: ppo_kernel divides M2 by its row
+// count `rows` (PpoArgs::n), so it standardises with sqrt(M2 / *count), the deviation of all ranks'
+// rows.  *count == rows: the factor is exactly 1 and the moments pass through bit for bit.
+__global__ void ppo_moments_rescale_kernel(const double* __restrict__ mom, double rows, const double* __restrict__ count,
+                                           double* __restrict__ out, const uint32_t* __restrict__ gate) {
+    if (gate && *gate != 0u) return;
+    out[0] = mom[0];
+    out[1] = mom[1] * (rows / *count);
+}
+
 static uint32_t ppo_blocks(uint32_t m) {
     const uint32_t tiles = (m + 15u) / 16u, want = (tiles + PPO_WAVES - 1) / PPO_WAVES;
     return want < PPO_MAX_BLOCKS ? want : PPO_MAX_BLOCKS;
@@ -561,6 +601,50 @@ static int ppo_launch(PpoArgs a, float* grad, double* summary, void* scratch, hi
 }
 
 static bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1u)) != 0; }
+
+// the fixed size of a rank-partial block: the head and the larger (value) slice
+template <int D>
+constexpr uint32_t ppo_partial_doubles() { return PPO_SUM + PpoNet<D, false>::NPAR; }
+static_assert(PpoNet<34, false>::NPAR >= PpoNet<34, true>::NPAR + 6 && PpoNet<42, false>::NPAR >= PpoNet<42, true>::NPAR + 6,
+              "the policy call's rescaled moments fit behind its block partials in the scratch");
+
+// the second launch of the rank-partial calls (m == 0: the only one, a zeroed block)
+template <int D, bool PI>
+static int partial_merge_launch(const float* part_grad, const double* part_sum, uint32_t blocks, uint32_t m,
+                                bool with_grad, double* out, const uint32_t* gate, hipStream_t s) {
+    constexpr uint32_t words = ppo_partial_doubles<D>() - PPO_SUM;
+    hipLaunchKernelGGL(ppo_partial_merge_kernel, dim3((words + 255u) / 256u), dim3(256), 0, s, part_grad, part_sum, blocks,
+                       (uint32_t)PpoNet<D, PI>::NPAR, words, m, with_grad ? 1 : 0, out, gate);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? CF2_OK : hip_fail(e);
+}
+
+// count: the device word holding the rows adv_moments was taken over (policy with adv_moments only)
+template <int D, bool PI>
+static int ppo_partial_launch(PpoArgs a, bool with_grad, const double* count, double* out, void* scratch,
+                              hipStream_t s) {
+    using N = PpoNet<D, PI>;
+    const uint32_t blocks = ppo_blocks(a.m);
+    a.part_sum = static_cast<double*>(scratch);
+    a.part_grad = reinterpret_cast<float*>(a.part_sum + (size_t)PPO_MAX_BLOCKS * PPO_SUM);
+    if (blocks == 0) return partial_merge_launch<D, PI>(nullptr, nullptr, 0, 0, false, out, a.gate, s);
+    if (PI && a.adv_moments) {
+        // behind the block partials, 8-byte aligned: the scratch is sized for the value slice
+        double* mom = reinterpret_cast<double*>(a.part_grad + (((size_t)blocks * N::NPAR + 1u) & ~(size_t)1u));
+        hipLaunchKernelGGL(ppo_moments_rescale_kernel, dim3(1), dim3(1), 0, s, a.adv_moments, (double)a.n, count, mom,
+                           a.gate);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e);
+        a.adv_moments = mom;
+    }
+    if (with_grad)
+        hipLaunchKernelGGL((ppo_kernel<D, PI, true>), dim3(blocks), dim3(PPO_BLOCK), 0, s, a);
+    else
+        hipLaunchKernelGGL((ppo_kernel<D, PI, false>), dim3(blocks), dim3(PPO_BLOCK), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e);
+    return partial_merge_launch<D, PI>(a.part_grad, a.part_sum, blocks, a.m, with_grad, out, a.gate, s);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Fisher-vector product of the policy (the natural-gradient updates, cf2sim_natgrad.hip).  For a
@@ -963,6 +1047,18 @@ static int fisher_launch(FisherArgs a, float* out, double* summary, void* scratc
     return e == hipSuccess ? CF2_OK : hip_fail(e);
 }
 
+template <int D>
+static int fisher_partial_launch(FisherArgs a, double* out, void* scratch, hipStream_t s) {
+    const uint32_t blocks = ppo_blocks(a.m);
+    a.part_sum = static_cast<double*>(scratch);
+    a.part_grad = reinterpret_cast<float*>(a.part_sum + (size_t)PPO_MAX_BLOCKS * PPO_SUM);
+    if (blocks == 0) return partial_merge_launch<D, true>(nullptr, nullptr, 0, 0, false, out, a.gate, s);
+    hipLaunchKernelGGL((ppo_fisher_kernel<D>), dim3(blocks), dim3(PPO_BLOCK), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e);
+    return partial_merge_launch<D, true>(a.part_grad, a.part_sum, blocks, a.m, true, out, a.gate, s);
+}
+
 }  // namespace cf2
 
 using namespace cf2;
@@ -1046,4 +1142,69 @@ extern "C" int cf2_ppo_fisher_vec(const float* weights_dev, uint32_t obs_dim, co
     const hipStream_t s = (hipStream_t)stream;
     return obs_dim == 34 ? fisher_launch<34>(a, out_dev, summary_dev, scratch_dev, s)
                          : fisher_launch<42>(a, out_dev, summary_dev, scratch_dev, s);
+}
+
+// ---- rank partials (include/cf2sim.h: "Data-parallel updates")
+extern "C" size_t cf2_ppo_partial_doubles(uint32_t obs_dim) {
+    return obs_dim == 34 ? ppo_partial_doubles<34>() : obs_dim == 42 ? ppo_partial_doubles<42>() : 0;
+}
+
+extern "C" int cf2_ppo_policy_partial(const float* weights_dev, uint32_t obs_dim, const float* obs_dev, const float* act_dev,
+                                      const float* logp_old_dev, const float* adv_dev, uint32_t n, const uint32_t* idx_dev,
+                                      uint32_t m, const double* adv_moments_dev, const double* moments_count_dev, float clip_ratio,
+                                      const float* mu_old_dev, float* mu_out_dev, float* logp_out_dev, int with_grad,
+                                      double* partial_dev, void* scratch_dev, const uint32_t* ctrl_dev, void* stream) {
+    if (obs_dim != 34 && obs_dim != 42) return CF2_ERR_UNSUPPORTED;
+    if (!partial_dev || misaligned(partial_dev, 8) || misaligned(ctrl_dev, 4)) return CF2_ERR_INVALID_ARG;
+    if (m != 0) {
+        if (!weights_dev || !obs_dev || !act_dev || !logp_old_dev || !adv_dev || !scratch_dev || n == 0 ||
+            (!idx_dev && m > n) || (adv_moments_dev && !moments_count_dev))
+            return CF2_ERR_INVALID_ARG;
+        if (misaligned(weights_dev, 4) || misaligned(obs_dev, 8) || misaligned(act_dev, 16) || misaligned(logp_old_dev, 4) ||
+            misaligned(adv_dev, 4) || misaligned(idx_dev, 4) || misaligned(adv_moments_dev, 8) || misaligned(moments_count_dev, 8) ||
+            misaligned(mu_old_dev, 4) || misaligned(mu_out_dev, 4) || misaligned(logp_out_dev, 4) || misaligned(scratch_dev, 8))
+            return CF2_ERR_INVALID_ARG;
+    }
+    PpoArgs a = {weights_dev, obs_dev, act_dev, logp_old_dev, adv_dev, idx_dev, adv_moments_dev, mu_old_dev, mu_out_dev,
+                 logp_out_dev, nullptr, nullptr, n, m, clip_ratio, ctrl_dev};
+    const hipStream_t s = (hipStream_t)stream;
+    return obs_dim == 34 ? ppo_partial_launch<34, true>(a, with_grad != 0, moments_count_dev, partial_dev, scratch_dev, s)
+                         : ppo_partial_launch<42, true>(a, with_grad != 0, moments_count_dev, partial_dev, scratch_dev, s);
+}
+
+extern "C" int cf2_ppo_value_partial(const float* weights_dev, uint32_t obs_dim, const float* obs_dev,
+                                     const float* target_dev, uint32_t n, const uint32_t* idx_dev, uint32_t m,
+                                     float* val_out_dev, int with_grad, double* partial_dev, void* scratch_dev,
+                                     const uint32_t* ctrl_dev, void* stream) {
+    if (obs_dim != 34 && obs_dim != 42) return CF2_ERR_UNSUPPORTED;
+    if (!partial_dev || misaligned(partial_dev, 8) || misaligned(ctrl_dev, 4)) return CF2_ERR_INVALID_ARG;
+    if (m != 0) {
+        if (!weights_dev || !obs_dev || !target_dev || !scratch_dev || n == 0 || (!idx_dev && m > n))
+            return CF2_ERR_INVALID_ARG;
+        if (misaligned(weights_dev, 4) || misaligned(obs_dev, 8) || misaligned(target_dev, 4) || misaligned(idx_dev, 4) ||
+            misaligned(val_out_dev, 4) || misaligned(scratch_dev, 8))
+            return CF2_ERR_INVALID_ARG;
+    }
+    PpoArgs a = {weights_dev, obs_dev, nullptr, nullptr, target_dev, idx_dev, nullptr, nullptr, nullptr, val_out_dev,
+                 nullptr, nullptr, n, m, 0.0f, ctrl_dev};
+    const hipStream_t s = (hipStream_t)stream;
+    return obs_dim == 34 ? ppo_partial_launch<34, false>(a, with_grad != 0, nullptr, partial_dev, scratch_dev, s)
+                         : ppo_partial_launch<42, false>(a, with_grad != 0, nullptr, partial_dev, scratch_dev, s);
+}
+
+extern "C" int cf2_ppo_fisher_partial(const float* weights_dev, uint32_t obs_dim, const float* obs_dev, uint32_t n,
+                                      const uint32_t* idx_dev, uint32_t m, const float* vec_dev, double* partial_dev,
+                                      void* scratch_dev, const uint32_t* ctrl_dev, void* stream) {
+    if (obs_dim != 34 && obs_dim != 42) return CF2_ERR_UNSUPPORTED;
+    if (!partial_dev || misaligned(partial_dev, 8) || misaligned(ctrl_dev, 4)) return CF2_ERR_INVALID_ARG;
+    if (m != 0) {
+        if (!weights_dev || !obs_dev || !vec_dev || !scratch_dev || n == 0 || (!idx_dev && m > n)) return CF2_ERR_INVALID_ARG;
+        if (misaligned(weights_dev, 4) || misaligned(obs_dev, 8) || misaligned(idx_dev, 4) || misaligned(vec_dev, 4) ||
+            misaligned(scratch_dev, 8))
+            return CF2_ERR_INVALID_ARG;
+    }
+    FisherArgs a = {weights_dev, vec_dev, obs_dev, idx_dev, nullptr, nullptr, n, m, ctrl_dev};
+    const hipStream_t s = (hipStream_t)stream;
+    return obs_dim == 34 ? fisher_partial_launch<34>(a, partial_dev, scratch_dev, s)
+                         : fisher_partial_launch<42>(a, partial_dev, scratch_dev, s);
 }

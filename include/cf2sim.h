@@ -497,6 +497,74 @@ int  cf2_ppo_fisher_vec(const float* weights_dev, uint32_t obs_dim, const float*
                         const uint32_t* idx_dev, uint32_t m, const float* vec_dev, float* out_dev,
                         double* summary_dev, void* scratch_dev, const uint32_t* ctrl_dev, void* stream);
 
+/* Data-parallel updates: the gradient, evaluation and Fisher-vector calls above in two levels, so that
+ * the ranks of a node update from all rows.  Level one, per rank: cf2_ppo_policy_partial,
+ * cf2_ppo_value_partial and cf2_ppo_fisher_partial run the first launch of cf2_ppo_policy_grad_gated,
+ * cf2_ppo_value_grad and cf2_ppo_fisher_vec (the same kernels on the same arguments) and end in a merge
+ * that writes, instead of grad and summary, one rank-partial block of cf2_ppo_partial_doubles(obs_dim)
+ * doubles (8 + the value slice's words, the larger slice, so one all-gather shape serves the three
+ * calls; 0 for an unsupported obs_dim) to partial_dev (8-byte aligned):
+ *   [0]     m, the rank's selected rows
+ *   [1..7]  the fp64 sums over those rows of the summary slots 1..7 (not divided)
+ *   [8 + p] the fp64 sum of word p of the network's slice of the gradient (pi W1 b1 W2 b2 W3 b3, or v
+ *           likewise) or of F vec: the block partials summed in block-index order, not divided by m
+ *           and not rounded to fp32; the words past the slice, and all of them when with_grad == 0
+ *           (evaluate only), are 0.
+ * m == 0 is legal: a rank may own no selected row.  Then only partial_dev (and ctrl_dev) are looked
+ * at, one launch writes a zeroed block, and the optional outputs are left untouched.
+ * moments_count_dev (policy, required with adv_moments_dev; 8-byte aligned): one double on the device,
+ * the rows adv_moments_dev was taken over -- all ranks' rows after cf2_moments_combine, whose output
+ * block is {count, mean, M2}, not the n rows of this rank -- so that A = (adv - mean) / (sqrt(M2 /
+ * count) + 1e-8).  A one-thread launch ahead of the gradient kernel writes {mean, M2 (n / count)} into
+ * the scratch for it; with count == n the factor is exactly 1 and the call is
+ * cf2_ppo_policy_grad_gated's arithmetic bit for bit.  The count stays on the device so that an update
+ * never waits for it.  ctrl_dev: the gate of cf2_ppo_policy_grad_gated (NULL or ctrl_dev[0] == 0: run; otherwise
+ * every launch returns at once and nothing is written).  scratch_dev: cf2_ppo_scratch_bytes(m, obs_dim)
+ * bytes.  Errors as the single-rank calls, plus a NULL or misaligned partial_dev and adv_moments_dev
+ * without moments_count_dev: CF2_ERR_INVALID_ARG.  Every error returns before anything is launched.
+ *
+ * Level two, on every rank after an all-gather of the blocks: cf2_ppo_reduce reads blocks_dev
+ * [world][cf2_ppo_partial_doubles(obs_dim)] in rank order, sums them in that order in fp64, divides by
+ * M = sum of the [0] words and rounds once, and writes exactly what the single-rank call writes: the
+ * pi (value == 0) or v (value != 0) slice of grad_dev (a whole flat block; NULL: the summary only) and
+ * summary_dev, 8 doubles, [0] = M.  One launch, no atomics: the same blocks give the same bits, so
+ * every rank holds the same grad and summary.  world == 1 gives the bits of the single-rank call (the
+ * same order of sums, one division, one rounding).  Splitting the same rows differently over ranks
+ * changes which 16-row tiles share a block's fp32 partial, so the bits differ between splits; each
+ * split meets the accuracy rule of the single-rank calls against fp64.  ctrl_dev: the gate, as above.
+ * The row counts are on the device: with M == 0 the launch writes nothing.  obs_dim not 34 or 42:
+ * CF2_ERR_UNSUPPORTED; world == 0, a NULL blocks_dev or summary_dev, a misaligned pointer (8 bytes; 4 for
+ * grad_dev and ctrl_dev): CF2_ERR_INVALID_ARG, before anything is launched. */
+size_t cf2_ppo_partial_doubles(uint32_t obs_dim);
+int  cf2_ppo_policy_partial(const float* weights_dev, uint32_t obs_dim, const float* obs_dev, const float* act_dev,
+                            const float* logp_old_dev, const float* adv_dev, uint32_t n, const uint32_t* idx_dev,
+                            uint32_t m, const double* adv_moments_dev, const double* moments_count_dev, float clip_ratio,
+                            const float* mu_old_dev, float* mu_out_dev, float* logp_out_dev, int with_grad,
+                            double* partial_dev, void* scratch_dev, const uint32_t* ctrl_dev, void* stream);
+int  cf2_ppo_value_partial(const float* weights_dev, uint32_t obs_dim, const float* obs_dev, const float* target_dev,
+                           uint32_t n, const uint32_t* idx_dev, uint32_t m, float* val_out_dev, int with_grad,
+                           double* partial_dev, void* scratch_dev, const uint32_t* ctrl_dev, void* stream);
+int  cf2_ppo_fisher_partial(const float* weights_dev, uint32_t obs_dim, const float* obs_dev, uint32_t n,
+                            const uint32_t* idx_dev, uint32_t m, const float* vec_dev, double* partial_dev,
+                            void* scratch_dev, const uint32_t* ctrl_dev, void* stream);
+int  cf2_ppo_reduce(const double* blocks_dev, uint32_t world, uint32_t obs_dim, int value, float* grad_dev,
+                    double* summary_dev, const uint32_t* ctrl_dev, void* stream);
+
+/* Batch moments across ranks.  cf2_column_moments_partial is cf2_column_moments writing a rank's
+ * moments block {count, mean[D], M2[D]} (1 + 2 D doubles, 8-byte aligned; count = rows) to block_dev;
+ * rows == 0 is legal and writes a zeroed block.  cf2_moments_combine folds blocks_dev [world][1 + 2 D]
+ * left in rank order, in fp64, with the update of Chan et al. (n = na + nb, delta = mean_b - mean_a,
+ * mean = mean_a + delta nb / n, M2 = M2_a + M2_b + delta^2 na nb / n) into out_dev, one block of the same
+ * layout.  Blocks of count 0 are skipped and the first block that counts is taken as it stands: world
+ * == 1 returns its input bit for bit, and no block counting gives {0, 0.., 0..}.  D = 1 serves the
+ * advantages (out_dev + 1 is the adv_moments_dev of cf2_ppo_policy_partial, out_dev its
+ * moments_count_dev) and the discounted returns, D = obs_dim the observations.  One launch of one
+ * workgroup; the same blocks give the same bits.  D == 0 or D > 64, world == 0, a NULL or misaligned
+ * (8 bytes) pointer: CF2_ERR_INVALID_ARG, before anything is launched. */
+int  cf2_column_moments_partial(const float* x_dev, uint64_t rows, uint32_t D, double* block_dev, void* scratch_dev,
+                                void* stream);
+int  cf2_moments_combine(const double* blocks_dev, uint32_t world, uint32_t D, double* out_dev, void* stream);
+
 /* The solver of the natural-gradient updates on a slice [begin, begin + count) of flat blocks, with
  * every scalar on the device: ng_state_dev, CF2_NG_STATE_DOUBLES doubles. */
 enum { CF2_NG_RDOTR = 0,        /* r.r of the conjugate-gradient recurrence (cg_init: b.b) */
