@@ -5,15 +5,22 @@ phoenix_drone_simulation, the package of Hu-Hanyang/disturbance-CrazyFile-simula
 * ``make(id)``: single-env gym-style adapter with the reference's ids, spaces and 4-tuple API.
 * ``cf2sim.physics``: the reference's physics plugin classes (``PybulletPhysicsWithAdversary``, ...,
   ``HipBatchedPhysics``) over the HIP physics kernel, for ``getattr(module, physics)`` lookups.
+* ``solve_value_tables(cfg)``: the HJ-adversary envs' value tables, solved on the GPU (hj_solve.py).
 """
 from .config import (ENV_SPECS, OUT_OF_SCOPE_IDS, REFERENCE_IDS, CF2Config, build_config,  # noqa: F401
                      spec_for_id)
 
 __all__ = ["ENV_SPECS", "REFERENCE_IDS", "OUT_OF_SCOPE_IDS", "CF2Config", "build_config", "spec_for_id",
-           "BatchedCrazyflieEnv", "make", "registry"]
+           "BatchedCrazyflieEnv", "make", "registry",
+           "HJModel", "default_target", "time_step", "solve_value_table", "solve_value_tables", "save_value_tables"]
+
+_HJ_SOLVE = ("HJModel", "default_target", "time_step", "solve_value_table", "solve_value_tables", "save_value_tables")
 
 
 def __getattr__(name):   # lazy: importing the package must not require torch / a GPU
+    if name in _HJ_SOLVE:    # HJ value-table generation (hj_solve.py)
+        from . import hj_solve
+        return getattr(hj_solve, name)
     if name == "BatchedCrazyflieEnv":
         from .vec_env import BatchedCrazyflieEnv
         return BatchedCrazyflieEnv

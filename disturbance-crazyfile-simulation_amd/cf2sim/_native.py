@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = (
     "cf2_xchg_publish", "cf2_xchg_wait_free", "cf2_xchg_wait", "cf2_xchg_pred_to_host", "cf2_xchg_begin", "cf2_xchg_step", "cf2_xchg_end", "cf2_xchg_env_step", "cf2_xchg_run",
     "cf2_xchg_host_times", "cf2_xchg_copy_sync",
     "cf2_xchg_recv_words",
+    "cf2_hj_model_sizeof", "cf2_hj_time_step", "cf2_hj_solve",
 )
 
 
@@ -48,7 +49,15 @@ class CF2Layout(ctypes.Structure):
         "num_params", "f_motor_lo")]
 
 
-CF2_ERR_UNSUPPORTED = -4      # include/cf2sim.h cf2_status
+class CF2HJModel(ctypes.Structure):
+    """include/cf2sim.h cf2_hj_model (cf2sim.hj_solve.HJModel fills it)."""
+    _fields_ = [("n", ctypes.c_uint32 * 6), ("grid_min", ctypes.c_double * 6), ("dx", ctypes.c_double * 6),
+                ("periodic_mask", ctypes.c_uint32), ("inertia", ctypes.c_double * 3), ("umax", ctypes.c_double * 3),
+                ("dmax", ctypes.c_double * 3), ("u_max_player", ctypes.c_int32), ("d_max_player", ctypes.c_int32)]
+
+
+CF2_ERR_INVALID_ARG = -1      # include/cf2sim.h cf2_status
+CF2_ERR_UNSUPPORTED = -4
 # include/cf2sim.h CF2_STORE_*: the cache policy of a store (cf2_store_policy)
 STORE_PLAIN, STORE_NT, STORE_WT, STORE_NT_WT = 0, 2, 16, 18
 
@@ -158,14 +167,20 @@ def load() -> ctypes.CDLL:
     lib.cf2_xchg_run.argtypes = [vp, vp, ctypes.c_uint64, u32, u32, u32, vp, u32, vp, vp, vp, vp, vp, vp]
     lib.cf2_xchg_host_times.argtypes = [vp, vp, u32, vp, ctypes.c_int]
     lib.cf2_xchg_copy_sync.argtypes = [vp, vp]
+    lib.cf2_hj_model_sizeof.restype = ctypes.c_size_t
+    lib.cf2_hj_time_step.argtypes = [P(CF2HJModel), ctypes.c_double, P(ctypes.c_double)]
+    lib.cf2_hj_solve.argtypes = [P(CF2HJModel), vp, vp, u32, ctypes.c_double, ctypes.c_double, ctypes.c_int, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         if name not in ("cf2_abi_version", "cf2_config_sizeof", "cf2_status_string", "cf2_last_hip_error",
                         "cf2_policy_weights_count", "cf2_policy_packed_count", "cf2_obs_packed_words",
                         "cf2_xchg_send_words", "cf2_xchg_recv_words", "cf2_episode_stats_scratch_bytes",
-                        "cf2_column_moments_scratch_bytes", "cf2_ppo_scratch_bytes", "cf2_ppo_partial_doubles"):
+                        "cf2_column_moments_scratch_bytes", "cf2_ppo_scratch_bytes", "cf2_ppo_partial_doubles",
+                        "cf2_hj_model_sizeof"):
             getattr(lib, name).restype = ctypes.c_int
     if lib.cf2_config_sizeof() != ctypes.sizeof(CF2Config):
         raise CF2Error(f"cf2_config size mismatch: C {lib.cf2_config_sizeof()} vs Python {ctypes.sizeof(CF2Config)}")
+    if lib.cf2_hj_model_sizeof() != ctypes.sizeof(CF2HJModel):
+        raise CF2Error(f"cf2_hj_model size mismatch: C {lib.cf2_hj_model_sizeof()} vs Python {ctypes.sizeof(CF2HJModel)}")
     _lib = lib
     return lib
 

@@ -567,4 +567,115 @@ int cf2_hj_disturbance(const cf2_config* cfg, const float* V_dev, const float* s
     return e == hipSuccess ? CF2_OK : hip_fail(e);
 }
 
+// ---- HJ reachability solver: the host half (model checks, fp64 tables, time step) ----
+size_t cf2_hj_model_sizeof(void) { return sizeof(cf2_hj_model); }
+
+// fills everything of the kernel arguments that the model determines
+static int hj_solve_args(const cf2_hj_model* m, HjSolveArgs* A) {
+    if (!m) return CF2_ERR_INVALID_ARG;
+    uint64_t total = 1;
+    for (int d = 0; d < 6; ++d) {
+        if (m->n[d] < 3u) return CF2_ERR_INVALID_ARG;
+        total *= m->n[d];
+        if (total >= (1ull << 31)) return CF2_ERR_INVALID_ARG;
+        if (!(m->dx[d] > 0.0) || !isfinite(m->dx[d]) || !isfinite(m->grid_min[d])) return CF2_ERR_INVALID_ARG;
+    }
+    for (int k = 0; k < 3; ++k) {
+        if (!(m->inertia[k] > 0.0) || !isfinite(m->inertia[k])) return CF2_ERR_INVALID_ARG;
+        if (!(m->umax[k] >= 0.0) || !isfinite(m->umax[k])) return CF2_ERR_INVALID_ARG;
+        if (!(m->dmax[k] >= 0.0) || !isfinite(m->dmax[k])) return CF2_ERR_INVALID_ARG;
+    }
+    for (int d = 0; d < 6; ++d)
+        if (m->n[d] > (uint32_t)HJS_MAX_PTS) return CF2_ERR_UNSUPPORTED;
+    memset(A, 0, sizeof(*A));
+    A->total = (uint32_t)total;
+    A->periodic_mask = m->periodic_mask & 63u;
+    uint32_t stride = 1;
+    for (int d = 5; d >= 0; --d) {
+        A->n[d] = m->n[d];
+        A->stride[d] = stride;
+        stride *= m->n[d];
+        A->inv_dx[d] = 1.0 / m->dx[d];
+        A->magic[d] = (uint32_t)(((1ull << 32) + m->n[d] - 1u) / m->n[d]);
+    }
+    A->cube = A->n[3] * A->n[4] * A->n[5];
+    const double* I = m->inertia;
+    A->c[0] = (I[1] - I[2]) / I[0];
+    A->c[1] = (I[2] - I[0]) / I[1];
+    A->c[2] = (I[0] - I[1]) / I[2];
+    const double su = m->u_max_player ? 1.0 : -1.0, sd = m->d_max_player ? 1.0 : -1.0;
+    for (int k = 0; k < 3; ++k) {
+        A->b[k] = (su * m->umax[k] + sd * m->dmax[k]) / I[k];
+        A->B[k] = (m->umax[k] + m->dmax[k]) / I[k];
+    }
+    for (uint32_t k = 0; k < m->n[0]; ++k) {
+        const double phi = m->grid_min[0] + (double)k * m->dx[0];
+        A->tab[HJS_SIN_PHI][k] = sin(phi);
+        A->tab[HJS_COS_PHI][k] = cos(phi);
+    }
+    for (uint32_t k = 0; k < m->n[1]; ++k) {
+        const double theta = m->grid_min[1] + (double)k * m->dx[1];
+        A->tab[HJS_TAN_THETA][k] = tan(theta);
+        A->tab[HJS_SEC_THETA][k] = 1.0 / cos(theta);
+    }
+    for (int d = 3; d < 6; ++d)
+        for (uint32_t k = 0; k < m->n[d]; ++k) A->tab[HJS_RATE_P + d - 3][k] = m->grid_min[d] + (double)k * m->dx[d];
+    return CF2_OK;
+}
+
+int cf2_hj_time_step(const cf2_hj_model* model, double cfl, double* dt_out) {
+    if (!dt_out || !(cfl > 0.0) || !isfinite(cfl)) return CF2_ERR_INVALID_ARG;
+    HjSolveArgs A;
+    const int st = hj_solve_args(model, &A);
+    if (st != CF2_OK) return st;
+    // the drift does not depend on psi: the maximum runs over the (phi, theta, p, q, r) combinations
+    double worst = 0.0;
+    for (uint32_t i0 = 0; i0 < A.n[0]; ++i0)
+        for (uint32_t i1 = 0; i1 < A.n[1]; ++i1) {
+            const double sphi = A.tab[HJS_SIN_PHI][i0], cphi = A.tab[HJS_COS_PHI][i0];
+            const double tth = A.tab[HJS_TAN_THETA][i1], scth = A.tab[HJS_SEC_THETA][i1];
+            for (uint32_t i3 = 0; i3 < A.n[3]; ++i3)
+                for (uint32_t i4 = 0; i4 < A.n[4]; ++i4)
+                    for (uint32_t i5 = 0; i5 < A.n[5]; ++i5) {
+                        const double p = A.tab[HJS_RATE_P][i3], q = A.tab[HJS_RATE_Q][i4], r = A.tab[HJS_RATE_R][i5];
+                        const double mix = q * sphi + r * cphi;
+                        double sum = fabs(p + mix * tth) * A.inv_dx[0];
+                        sum += fabs(q * cphi - r * sphi) * A.inv_dx[1];
+                        sum += fabs(mix * scth) * A.inv_dx[2];
+                        sum += (fabs(A.c[0] * (q * r)) + A.B[0]) * A.inv_dx[3];
+                        sum += (fabs(A.c[1] * (p * r)) + A.B[1]) * A.inv_dx[4];
+                        sum += (fabs(A.c[2] * (p * q)) + A.B[2]) * A.inv_dx[5];
+                        if (!(sum <= worst)) worst = sum;
+                    }
+        }
+    if (!(worst > 0.0) || !isfinite(worst)) return CF2_ERR_INVALID_ARG;   // e.g. a grid through cos(theta) = 0
+    *dt_out = cfl / worst;
+    return CF2_OK;
+}
+
+int cf2_hj_solve(const cf2_hj_model* model, double* w_dev, double* tmp_dev, uint32_t steps, double dt, double dt_last,
+                 int tube, float* table_out_dev, double* change_dev, void* stream) {
+    if (!w_dev || !tmp_dev || w_dev == tmp_dev) return CF2_ERR_INVALID_ARG;
+    if (!(dt > 0.0) || !isfinite(dt) || !(dt_last > 0.0) || !isfinite(dt_last)) return CF2_ERR_INVALID_ARG;
+    if (((uintptr_t)w_dev & 7u) || ((uintptr_t)tmp_dev & 7u) || ((uintptr_t)change_dev & 7u) ||
+        ((uintptr_t)table_out_dev & 3u))
+        return CF2_ERR_INVALID_ARG;
+    HjSolveArgs A;
+    const int st = hj_solve_args(model, &A);
+    if (st != CF2_OK) return st;
+    // no buffer may overlap another: w and tmp hold total doubles, the table total floats, change one double
+    const uintptr_t w0 = (uintptr_t)w_dev, t0 = (uintptr_t)tmp_dev, wb = (uintptr_t)A.total * sizeof(double);
+    const uintptr_t o0 = (uintptr_t)table_out_dev, ob = (uintptr_t)A.total * sizeof(float);
+    const uintptr_t c0 = (uintptr_t)change_dev, cb = sizeof(double);
+    auto overlap = [](uintptr_t a, uintptr_t an, uintptr_t b, uintptr_t bn) { return a < b + bn && b < a + an; };
+    if (overlap(w0, wb, t0, wb)) return CF2_ERR_INVALID_ARG;
+    if (o0 && (overlap(o0, ob, w0, wb) || overlap(o0, ob, t0, wb))) return CF2_ERR_INVALID_ARG;
+    if (c0 && (overlap(c0, cb, w0, wb) || overlap(c0, cb, t0, wb) || (o0 && overlap(c0, cb, o0, ob))))
+        return CF2_ERR_INVALID_ARG;
+    A.tube = tube ? 1 : 0;
+    const hipError_t e = launch_hj_solve(A, w_dev, tmp_dev, steps, dt, dt_last, table_out_dev, change_dev,
+                                         (hipStream_t)stream);
+    return e == hipSuccess ? CF2_OK : hip_fail(e);
+}
+
 }  // extern "C"

@@ -204,4 +204,28 @@ hipError_t launch_hj(const HjGrid& G, const double umax[3], const float* V, cons
 // the sign bits hj_signs derives from the 7 taps around each grid node, for every node of every table
 hipError_t launch_hj_sign_table(const float* V, uint32_t num_tables, uint8_t* bits, hipStream_t s);
 
+// ---- HJ reachability solver (cf2sim_hjsolve.hip; cf2_hj_solve) ----
+// the per-dimension tables the host fills in fp64, by value in the kernel arguments (no device
+// table, no allocation): a dimension has at most HJS_MAX_PTS nodes
+constexpr int HJS_MAX_PTS = 48;
+enum { HJS_SIN_PHI = 0, HJS_COS_PHI, HJS_TAN_THETA, HJS_SEC_THETA, HJS_RATE_P, HJS_RATE_Q, HJS_RATE_R, HJS_TABLES };
+struct HjSolveArgs {
+    const double* src;          // set per launch by launch_hj_solve, like dst, dt and change
+    double* dst;
+    unsigned long long* change;
+    double dt;
+    uint32_t total, periodic_mask;
+    int32_t tube;
+    uint32_t cube;              // n[3] n[4] n[5], the nodes of one rate cube
+    uint32_t n[6], stride[6];
+    uint32_t magic[6];          // ceil(2^32 / n[d]): x / n[d] = umulhi(x, magic[d]) for x n[d] < 2^32
+    double inv_dx[6];
+    double c[3], b[3], B[3];    // rate dims 3..5: gyroscopic factor, signed and absolute input authority / inertia
+    double tab[HJS_TABLES][HJS_MAX_PTS];
+};
+// steps - 1 steps of dt and one of dt_last from w (ping-pong with tmp); the result ends in w, its
+// fp32 cast in table_out (optional), max |W' - W| of the last step in change[0] (optional)
+hipError_t launch_hj_solve(HjSolveArgs A, double* w, double* tmp, uint32_t steps, double dt, double dt_last,
+                           float* table_out, double* change, hipStream_t s);
+
 }  // namespace cf2

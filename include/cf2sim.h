@@ -750,6 +750,41 @@ int  cf2_xchg_copy_sync(cf2_xchg* x, const uint32_t* pred_host);
  * CF2_XCHG_HOST_TIMING=1 was set at cf2_xchg_create; reset != 0 clears them. */
 int  cf2_xchg_host_times(cf2_xchg* x, double* ns_out, uint32_t n_out, uint64_t* calls_out, int reset);
 
+/* HJ value-table generation (no reference counterpart in its repository: the reference's tables come
+ * from a solver that is not part of it, so parity with those tables is unpinned).  A backward
+ * reachability solve of the attitude / body-rate model
+ *   x = [roll phi, pitch theta, yaw psi, p, q, r]   (the C-order axes of a value table)
+ *   f0 = p + (q sin(phi) + r cos(phi)) tan(theta)     f3 = c3 q r + (u0 + d0) / Ixx   c3 = (Iyy - Izz) / Ixx
+ *   f1 = q cos(phi) - r sin(phi)                      f4 = c4 p r + (u1 + d1) / Iyy   c4 = (Izz - Ixx) / Iyy
+ *   f2 = (q sin(phi) + r cos(phi)) / cos(theta)       f5 = c5 p q + (u2 + d2) / Izz   c5 = (Ixx - Iyy) / Izz
+ *   |u_i| <= umax[i], |d_i| <= dmax[i]
+ * on the grid of n[0] x ... x n[5] nodes grid_min[d] + k dx[d] (bit d of periodic_mask: dimension d
+ * wraps, its upper end excluded).  u_max_player / d_max_player != 0: that input maximises the
+ * Hamiltonian, else it minimises.  The scheme (first-order per-node Lax-Friedrichs, forward Euler,
+ * fp64) is stated at the head of csrc/cf2sim_hjsolve.hip.
+ * cf2_hj_time_step (host only): dt = cfl / max over nodes of sum_d alpha_d(x) / dx[d], the scheme's
+ * monotonicity bound (alpha_d = |f_d| for d < 3, |c_d (product of the other rates)| + (umax + dmax) / I
+ * for d >= 3).
+ * cf2_hj_solve: steps - 1 steps of dt and one of dt_last from W = w_dev (the target function l, n[0] x
+ * ... x n[5] doubles in C order) by W_t = min(0, H) (tube != 0: a backward reachable tube) or W_t = H;
+ * the result ends in w_dev, tmp_dev (as large) is scratch.  table_out_dev (optional): W rounded to
+ * float32, the layout cf2_bind_hj_tables takes.  change_dev (optional, one double): max |W' - W| of
+ * the last step.  Asynchronous on the stream: a fixed sequence of launches, no host read.
+ * CF2_ERR_INVALID_ARG, before the device is touched, for null or aliased buffers, an n[d] < 3, 2^31 or
+ * more nodes, a dt, dx or inertia that is not positive, a negative umax or dmax; CF2_ERR_UNSUPPORTED for
+ * an n[d] above 48. */
+typedef struct cf2_hj_model {
+    uint32_t n[6];
+    double grid_min[6], dx[6];
+    uint32_t periodic_mask;
+    double inertia[3], umax[3], dmax[3];
+    int32_t u_max_player, d_max_player;
+} cf2_hj_model;
+size_t cf2_hj_model_sizeof(void);
+int  cf2_hj_time_step(const cf2_hj_model* model, double cfl, double* dt_out);
+int  cf2_hj_solve(const cf2_hj_model* model, double* w_dev, double* tmp_dev, uint32_t steps, double dt,
+                  double dt_last, int tube, float* table_out_dev, double* change_dev, void* stream);
+
 /* Measurement support (no reference counterpart): streaming kernels over `bytes` (a multiple of
  * 16, both pointers 16-B aligned) with non-temporal accesses.  mode 0: copy src -> dst; mode 1:
  * read src only (bytes >= 4096; dst must hold 4 KB and is normally left untouched).  bench.py times
