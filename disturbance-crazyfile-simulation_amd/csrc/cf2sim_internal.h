@@ -49,7 +49,8 @@ enum { NUM_PARAMS = 19 };
 // cf2_set_state stays the plain SoA above (F_* / I_* fields); conversion kernels map it.
 enum : int {
     S_POS = 0, S_QUAT = 3, S_VEL = 7, S_OMEGA = 10,      // G0-G3 (always read + written)
-    S_EP = 13, S_RNG = 14, S_FLAGS = 15,                  //   ints in G3
+    S_EP = 13, S_RNG = 14, S_FLAGS = 15,                  //   ints in G3 (S_FLAGS: I_FLAGS' bits 0-7 and, in
+                                                          //   memory only, bit 8 FL_RING_COMPACT, cf2sim_state.h)
     S_MOTOR = 16,                                         // G4
     S_OU = 20,                                            // G5
     S_ABUF = 24,                                          // G6-G9, row r in G6+r

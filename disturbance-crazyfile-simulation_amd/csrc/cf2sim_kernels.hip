@@ -740,6 +740,10 @@ __global__ void __launch_bounds__(256) physics_kernel(KParams P, float* __restri
     if (i >= P.N) return;
     Env E;
     load_env<NOISE, DR, PHYS>(P, sf, i, E, false, /*with_hist=*/false);
+    // one sub-step leaves the ring's rows unequal: a compact env goes back to explicit rows (store_core
+    // writes all of them, the flag word below has the bit clear) and its hact[1], ring row 0 as loaded,
+    // is materialised in G_HACT + 1
+    const F4 row0 = f4(E.abuf[0][0], E.abuf[0][1], E.abuf[0][2], E.abuf[0][3]);
     const float4 a4 = reinterpret_cast<const float4*>(act)[i];
     const float a[4] = {a4.x, a4.y, a4.z, a4.w};
     float d[3] = {0.0f, 0.0f, 0.0f};
@@ -768,6 +772,7 @@ __global__ void __launch_bounds__(256) physics_kernel(KParams P, float* __restri
     E.rng += 1;
     store_core<NOISE, DR, PHYS>(P, sf, i, E);
     const Tile T(sf, P.N, i);
+    if (E.compact) T.st(G_HACT + 1, row0);
     const int fl = (E.aidx & 15) | (E.halias0 << 4) | (E.halias1 << 5) | (E.la_view << 6) | (E.props_on << 7);
     T.st(G_CORE3, f4(E.w[2], ib(E.ep_step), ib((int)E.rng), ib(fl)));
 }
@@ -1290,12 +1295,20 @@ __device__ __forceinline__ int pub_int_slot(int f) {
 __device__ __forceinline__ size_t slot_index(uint32_t i, int slot) {     // in floats
     return (size_t)(i >> 6) * (NG * 256) + (size_t)(slot >> 2) * 256 + (i & 63u) * 4 + (slot & 3);
 }
+// The public snapshot is canonical: an env in the ring's compact form (FL_RING_COMPACT) exports
+// ring rows 1 .. ring_rows - 1 and hact[1] from row 0, and its flag word without the bit; an import
+// writes explicit rows and a clear bit.  ring_rows: the rows in use where the context's shape can
+// go compact (ring_compact_shape), else 0.
 __global__ void state_convert_kernel(uint32_t N, float* __restrict__ sf, float* __restrict__ pf,
-                                     int32_t* __restrict__ pi, int to_public, int noise) {
+                                     int32_t* __restrict__ pi, int to_public, int noise, int ring_rows) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
+    const bool compact =
+        to_public && ring_rows > 0 && (__float_as_int(sf[slot_index(i, S_FLAGS)]) & (int)FL_RING_COMPACT) != 0;
     for (int f = 0; f < NF; ++f) {
-        const int slot = pub_float_slot(f, noise != 0);
+        int slot = pub_float_slot(f, noise != 0);
+        if (compact && f >= F_ABUF + 4 && f < F_ABUF + 4 * ring_rows) slot = S_ABUF + ((f - F_ABUF) & 3);
+        if (compact && f >= F_HIST_ACT + 4 && f < F_HIST_ACT + 8) slot = S_ABUF + (f - (F_HIST_ACT + 4));
         if (slot == -2) {    // not stored: exported as 0, ignored on import
             if (to_public) pf[(size_t)f * N + i] = 0.0f;
             continue;
@@ -1310,8 +1323,9 @@ __global__ void state_convert_kernel(uint32_t N, float* __restrict__ sf, float* 
     }
     for (int f = 0; f < NI; ++f) {
         float* in = sf + slot_index(i, pub_int_slot(f));
-        if (to_public) pi[(size_t)f * N + i] = __float_as_int(*in);
-        else *in = __int_as_float(pi[(size_t)f * N + i]);
+        const int keep = f == I_FLAGS ? ~(int)FL_RING_COMPACT : ~0;
+        if (to_public) pi[(size_t)f * N + i] = __float_as_int(*in) & keep;
+        else *in = __int_as_float(pi[(size_t)f * N + i] & keep);
     }
 }
 
@@ -1619,7 +1633,9 @@ hipError_t launch_physics(const KParams& P, float* sf, const float* act, const f
 hipError_t launch_state_convert(const KParams& P, float* sf, float* state_f, int32_t* state_i, int to_public,
                                 hipStream_t s) {
     const dim3 grid = grid_of(P.N, 256), block(256);
-    hipLaunchKernelGGL(state_convert_kernel, grid, block, 0, s, P.N, sf, state_f, state_i, to_public, (int)P.noise);
+    const int ring_rows = P.use_latency != 0 && P.agg >= P.buf_size ? (int)P.buf_size : 0;
+    hipLaunchKernelGGL(state_convert_kernel, grid, block, 0, s, P.N, sf, state_f, state_i, to_public, (int)P.noise,
+                       ring_rows);
     return hipGetLastError();
 }
 hipError_t launch_init(const KParams& P, float* sf, hipStream_t s) {

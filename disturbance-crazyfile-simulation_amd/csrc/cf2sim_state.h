@@ -145,6 +145,8 @@ struct Env {
     int ep_step, aidx, halias0, halias1, la_view, props_on, level_idx, gust_left;
     uint32_t rng;
     float la[4];                    // drone.last_action
+    bool compact;                   // the state in memory is in the ring's compact form (FL_RING_COMPACT)
+    bool dstb_dirty;                // gust mode: the env-step changed dstb (store_core's store on change)
 };
 
 // ------------------------------------------------------------------------------------
@@ -177,6 +179,12 @@ struct TileT {
         const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(voff + (uint32_t)g * 1024u), 0, 0);
         return F4{__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)};
     }
+    // group ga in lanes where `first`, else gb: one load through a per-lane offset
+    __device__ __forceinline__ F4 ld_sel(bool first, int ga, int gb) const {
+        const uint32_t off = voff + (first ? (uint32_t)ga : (uint32_t)gb) * 1024u;
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
+        return F4{__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)};
+    }
     __device__ __forceinline__ void st(int g, F4 f) const {
         const u32x4 v = {__float_as_uint(f.x), __float_as_uint(f.y), __float_as_uint(f.z), __float_as_uint(f.w)};
         __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)(voff + (uint32_t)g * 1024u), 0, ST_AUX);
@@ -190,6 +198,17 @@ enum : int { G_CORE3 = 3, G_MOTOR = 4, G_OU = 5, G_ABUF = 6, G_BIAS = 10, G_LPF 
              G_HACT = 14, G_OBSP = 16, G_HELD = 21, G_PARAM = 24, G_LEVEL = 27, G_MOTOR_LO = 28,
              G_LEVEL_IDX = 29 };
 
+// The latency ring's compact form.  Where every env-step writes the whole ring (latency on and at
+// least as many sub-steps as rows), every row holds the step's action afterwards, and so does
+// hact[1] (compute_history).  Such a step stores the 16 B once, in G_ABUF + 0, and sets
+// FL_RING_COMPACT in the env's flag word: rows r >= 1 and G_HACT + 1 are then stale in memory and
+// every reader takes them from row 0 (load_env, load_hist, physics_kernel, state_convert_kernel).
+// The condition is launch-uniform; a shape that fails it never sets or honours the bit.  Resets,
+// whole-state stores (store_env) and imports write every row and clear the bit.
+enum : int { FL_RING_COMPACT = 1 << 8 };       // bits 0-7: I_FLAGS (cf2sim_internal.h)
+__device__ __forceinline__ bool ring_compact_shape(const KParams& P) {
+    return P.use_latency != 0 && P.agg >= P.buf_size;
+}
 __device__ __forceinline__ bool gust_mode(const KParams& P) { return P.dstb_mode == DSTB_GUST_T; }
 __device__ __forceinline__ bool dstb_stored(const KParams& P) {
     return P.dstb_mode == DSTB_CONST_T || P.dstb_mode == DSTB_GUST_T;
@@ -198,7 +217,10 @@ __device__ __forceinline__ bool dstb_stored(const KParams& P) {
 template <bool NOISE>
 __device__ __forceinline__ void load_hist(const Tile& T, Env& E) {
     constexpr int OL = NOISE ? 13 : 17;
-    const F4 h0 = T.ld(G_HACT), h1 = T.ld(G_HACT + 1);
+    // compact lanes: hact[1] is ring row 0.  In the one-step kernels this load is issued after the
+    // physics and before store_core overwrites G_ABUF + 0; the wave's own later store to the same
+    // address relies on the in-order vector-memory pipeline, as the other history loads do
+    const F4 h0 = T.ld(G_HACT), h1 = T.ld_sel(E.compact, G_ABUF, G_HACT + 1);
     E.hact[0][0] = h0.x; E.hact[0][1] = h0.y; E.hact[0][2] = h0.z; E.hact[0][3] = h0.w;
     E.hact[1][0] = h1.x; E.hact[1][1] = h1.y; E.hact[1][2] = h1.z; E.hact[1][3] = h1.w;
 #pragma unroll
@@ -225,6 +247,8 @@ __device__ __forceinline__ void load_env(const KParams& P, const float* __restri
     const int fl = bi(g3.w);
     E.aidx = fl & 15; E.halias0 = (fl >> 4) & 1; E.halias1 = (fl >> 5) & 1; E.la_view = (fl >> 6) & 1;
     E.props_on = (fl >> 7) & 1;
+    E.compact = ring_compact_shape(P) && (fl & FL_RING_COMPACT) != 0;
+    E.dstb_dirty = false;
     E.x[0] = gx.x; E.x[1] = gx.y; E.x[2] = gx.z; E.x[3] = gx.w;
     {
         F4 xl = f4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -236,6 +260,7 @@ __device__ __forceinline__ void load_env(const KParams& P, const float* __restri
     for (int r = 0; r < 4; ++r) {
         F4 a = f4(0.0f, 0.0f, 0.0f, 0.0f);
         if (r < P.buf_size) a = T.ld(G_ABUF + r);
+        if (r >= 1 && r < P.buf_size && E.compact) a = f4(E.abuf[0][0], E.abuf[0][1], E.abuf[0][2], E.abuf[0][3]);
         E.abuf[r][0] = a.x; E.abuf[r][1] = a.y; E.abuf[r][2] = a.z; E.abuf[r][3] = a.w;
     }
     E.gust_left = 0;
@@ -306,9 +331,14 @@ __device__ __forceinline__ void helper_wave_init(const KParams& P, const Tile& T
 
 // state the physics sub-steps update (stored as soon as the last sub-step is done; group 3,
 // which carries the counters, is stored with the history at the end of the step)
-template <bool NOISE, bool DR, int PHYS, int ST_AUX = 0>
+// STEP: the stores of an env-step (step_env_body): the ring in its compact form where the shape
+// allows it (store_tail sets the bit), and in gust mode G_DSTB only in lanes whose torque changed
+// (an onset, or the step after an expiry: ~2 % of env-steps at the default gust settings); the
+// bytes in memory are the same either way.  Without STEP every group and every row is written.
+template <bool NOISE, bool DR, int PHYS, int ST_AUX = 0, bool STEP = false>
 __device__ __forceinline__ void store_core(const KParams& P, float* __restrict__ sf, uint32_t i, const Env& E) {
     const TileT<ST_AUX> T(sf, P.N, i);
+    const bool once = STEP && ring_compact_shape(P);
     T.st(0, f4(E.p[0], E.p[1], E.p[2], E.q[0]));
     T.st(1, f4(E.q[1], E.q[2], E.q[3], E.v[0]));
     T.st(2, f4(E.v[1], E.v[2], E.w[0], E.w[1]));
@@ -317,7 +347,8 @@ __device__ __forceinline__ void store_core(const KParams& P, float* __restrict__
     T.st(G_OU, f4(E.ou[0], E.ou[1], E.ou[2], E.ou[3]));
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-        if (r < P.buf_size) T.st(G_ABUF + r, f4(E.abuf[r][0], E.abuf[r][1], E.abuf[r][2], E.abuf[r][3]));
+        if (r < P.buf_size && !(once && r >= 1))
+            T.st(G_ABUF + r, f4(E.abuf[r][0], E.abuf[r][1], E.abuf[r][2], E.abuf[r][3]));
     if (NOISE || gust_mode(P))
         T.st(G_BIAS, f4(NOISE ? E.bias[0] : 0.0f, NOISE ? E.bias[1] : 0.0f, NOISE ? E.bias[2] : 0.0f, ib(E.gust_left)));
     if (NOISE && P.held_persistent) {      // (the LPF state is stored with the history, store_tail)
@@ -326,7 +357,7 @@ __device__ __forceinline__ void store_core(const KParams& P, float* __restrict__
         T.st(G_HELD + 2, f4(E.held[8], E.held[9], 0.0f, 0.0f));
     }
     if (PHYS == PHYS_SIMPLE_T) T.st(G_RPY, f4(E.rpy[0], E.rpy[1], E.rpy[2], 0.0f));
-    if (gust_mode(P)) T.st(G_DSTB, f4(E.dstb[0], E.dstb[1], E.dstb[2], 0.0f));
+    if (gust_mode(P) && (!STEP || E.dstb_dirty)) T.st(G_DSTB, f4(E.dstb[0], E.dstb[1], E.dstb[2], 0.0f));
 }
 
 // the o_{k-1} groups; with sensor noise the last one carries the gyro LPF state
@@ -344,13 +375,16 @@ __device__ __forceinline__ void store_obs_prev(const TT& T, const Env& E) {
 }
 
 // end of the step: history, counters (group 3 with the last angular-rate component)
-template <bool NOISE, int ST_AUX = 0>
+// (STEP: as store_core; G_HACT + 0 is the previous hact[1] and is stored either way)
+template <bool NOISE, int ST_AUX = 0, bool STEP = false>
 __device__ __forceinline__ void store_tail(const KParams& P, float* __restrict__ sf, uint32_t i, const Env& E) {
     const TileT<ST_AUX> T(sf, P.N, i);
+    const bool once = STEP && ring_compact_shape(P);
     T.st(G_HACT, f4(E.hact[0][0], E.hact[0][1], E.hact[0][2], E.hact[0][3]));
-    T.st(G_HACT + 1, f4(E.hact[1][0], E.hact[1][1], E.hact[1][2], E.hact[1][3]));
+    if (!once) T.st(G_HACT + 1, f4(E.hact[1][0], E.hact[1][1], E.hact[1][2], E.hact[1][3]));
     store_obs_prev<NOISE>(T, E);
-    const int fl = (E.aidx & 15) | (E.halias0 << 4) | (E.halias1 << 5) | (E.la_view << 6) | (E.props_on << 7);
+    const int fl = (E.aidx & 15) | (E.halias0 << 4) | (E.halias1 << 5) | (E.la_view << 6) | (E.props_on << 7) |
+                   (once ? (int)FL_RING_COMPACT : 0);
     T.st(G_CORE3, f4(E.w[2], ib(E.ep_step), ib((int)E.rng), ib(fl)));
 }
 

@@ -110,6 +110,7 @@ __device__ __forceinline__ bool step_env_body(const KParams& P, const StepIO& io
         break;
     case DSTB_GUST_T: {
         const U4 u = g.block(0);
+        const float was[3] = {E.dstb[0], E.dstb[1], E.dstb[2]};       // as loaded
         if (E.gust_left == 0 && u01(u.x) < P.gust_p) {
             E.gust_left = P.gust_dur;
             const float mag = P.gust_max * u01(u.y);
@@ -124,6 +125,10 @@ __device__ __forceinline__ bool step_env_body(const KParams& P, const StepIO& io
 #pragma unroll
             for (int k = 0; k < 3; ++k) E.dstb[k] = 0.0f;
         }
+        // compared bitwise here, so that one flag and not the loaded words stays live to store_core
+        E.dstb_dirty = false;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) E.dstb_dirty |= __float_as_uint(E.dstb[k]) != __float_as_uint(was[k]);
         break;
     }
     case DSTB_HJ_T: {
@@ -201,7 +206,7 @@ __device__ __forceinline__ bool step_env_body(const KParams& P, const StepIO& io
     // so no two waves store one group in one launch.  The large-N kernel stores it anyway: its
     // resets follow __syncthreads, whose workgroup-scope release/acquire orders these stores before
     // the reset waves' stores to the same groups (skipping them cost 0.6 us there)
-    if (STORE && !(SKIP_RESETTING && do_reset)) store_core<NOISE, DR, PHYS, ST_AUX>(P, io.sf, i, E);
+    if (STORE && !(SKIP_RESETTING && do_reset)) store_core<NOISE, DR, PHYS, ST_AUX, true>(P, io.sf, i, E);
     const auto& IL = late_outputs_if<LATEP>(io);
     {
         const float r = compute_reward(PL, E, a, term);
@@ -232,7 +237,7 @@ __device__ __forceinline__ bool step_env_body(const KParams& P, const StepIO& io
         rs.ctr = E.rng;
     }
     E.rng += 1;
-    if (STORE && !(SKIP_RESETTING && do_reset)) store_tail<NOISE, ST_AUX>(P, io.sf, i, E);
+    if (STORE && !(SKIP_RESETTING && do_reset)) store_tail<NOISE, ST_AUX, true>(P, io.sf, i, E);
     TSTAMP(3);   // epilogue issued
     return do_reset;
 }

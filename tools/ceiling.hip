@@ -7,6 +7,8 @@
 // obs-shaped stores (plain, sc1 write-through, nt, nt sc1: the aux bits of the buffer stores), timed
 // back to back on one stream, every launch dependent on the one before (HIP events around `iters`
 // launches), to see what the stores' policy costs or saves at a kernel boundary without the physics.
+// `ceiling groups [N] [iters]`: 17 against 14 stored state groups under the write-through pair: the
+// bound on what storing fewer groups can gain (profiles/action_once_ab.txt).
 // build: hipcc --offload-arch=gfx950 -O3 -o ceiling tools/ceiling.hip
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -137,7 +139,7 @@ static void run_step(uint32_t N, int act_slabs) {
     CHECK(hipFree(st)); CHECK(hipFree(act)); CHECK(hipFree(obs)); CHECK(hipFree(rew)); CHECK(hipFree(done));
 }
 
-template <int SA, int OA>
+template <int SA, int OA, int WG = 17>
 static void run_policy(uint32_t N, int iters) {
     f4v *st, *act, *obs;
     float* rew;
@@ -155,9 +157,9 @@ static void run_policy(uint32_t N, int iters) {
     double us[3];
     for (int r = 0; r < 3; ++r)
         us[r] = time_us([&] {
-            step_like_pol<22, 17, SA, OA><<<N / 256, 256>>>(st, act + (size_t)(it++ % act_slabs) * N, obs, rew, done, N);
+            step_like_pol<22, WG, SA, OA><<<N / 256, 256>>>(st, act + (size_t)(it++ % act_slabs) * N, obs, rew, done, N);
         }, iters);
-    printf("step-like N=%8u R22 W17 state %-6s obs %-6s  %7.2f %7.2f %7.2f us (%d launches each)\n", N,
+    printf("step-like N=%8u R22 W%2d state %-6s obs %-6s  %7.2f %7.2f %7.2f us (%d launches each)\n", N, WG,
            SA == 0 ? "plain" : SA == 16 ? "sc1" : SA == 2 ? "nt" : "nt sc1",
            OA == 0 ? "plain" : OA == 16 ? "sc1" : OA == 2 ? "nt" : "nt sc1", us[0], us[1], us[2], iters);
     CHECK(hipFree(st)); CHECK(hipFree(act)); CHECK(hipFree(obs)); CHECK(hipFree(rew)); CHECK(hipFree(done));
@@ -171,6 +173,7 @@ static int policy_sweep(uint32_t N, int iters) {
         run_policy<16, 2>(N, iters);
         run_policy<0, 18>(N, iters);
         run_policy<16, 18>(N, iters);
+        run_policy<16, 18, 14>(N, iters);      // the wt pair with three fewer groups stored
         run_policy<16, 16>(N, iters);
         run_policy<2, 2>(N, iters);
         run_policy<2, 18>(N, iters);
@@ -179,14 +182,29 @@ static int policy_sweep(uint32_t N, int iters) {
     return 0;
 }
 
+// `ceiling groups [N] [iters]`: what three fewer stored groups are worth under the wt pair (state sc1,
+// obs nt sc1), W17 and W14 interleaved, five rounds
+static int groups_ab(uint32_t N, int iters) {
+    if (N == 0 || N % 256) { printf("N must be a positive multiple of 256\n"); return 1; }
+    for (int round = 0; round < 5; ++round) {
+        run_policy<16, 18, 17>(N, iters);
+        run_policy<16, 18, 14>(N, iters);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc > 1 && !strcmp(argv[1], "policy"))
         return policy_sweep(argc > 2 ? (uint32_t)atol(argv[2]) : 262144u, argc > 3 ? atoi(argv[3]) : 3000);
+    if (argc > 1 && !strcmp(argv[1], "groups"))
+        return groups_ab(argc > 2 ? (uint32_t)atol(argv[2]) : 262144u, argc > 3 ? atoi(argv[3]) : 3000);
     run_step<22, 17>(262144, 8);
+    run_step<22, 14>(262144, 8);
     run_step<22, 17>(262144, 1);
     run_step<20, 15>(262144, 8);
     run_step<18, 13>(262144, 8);
     run_step<22, 17>(65536, 8);
+    run_step<22, 14>(65536, 8);
     run_step<22, 17>(1048576, 8);
     run_step<22, 17>(4194304, 8);
     const size_t bytes = (size_t)1 << 30, n = bytes / 16;
