@@ -38,6 +38,8 @@ EXPORTED_SYMBOLS = (
     "cf2_xchg_host_times", "cf2_xchg_copy_sync",
     "cf2_xchg_recv_words",
     "cf2_hj_model_sizeof", "cf2_hj_time_step", "cf2_hj_solve",
+    "cf2_level_outcomes_scratch_bytes", "cf2_level_outcomes", "cf2_collect_step_info", "cf2_collect_rollout_info",
+    "cf2_set_level_distribution",
 )
 
 
@@ -100,6 +102,9 @@ def load() -> ctypes.CDLL:
                                      ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
     lib.cf2_collect_rollout.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, ctypes.c_uint32, ctypes.c_int,
                                         ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
+    lib.cf2_collect_step_info.argtypes = lib.cf2_collect_step.argtypes[:-1] + [vp, vp, vp]
+    lib.cf2_collect_rollout_info.argtypes = lib.cf2_collect_rollout.argtypes[:-1] + [vp, vp, vp]
+    lib.cf2_set_level_distribution.argtypes = [vp, P(ctypes.c_double), ctypes.c_int32]
     lib.cf2_set_ground_effect.argtypes = [vp, ctypes.c_int]
     lib.cf2_rollout.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cf2_get_state.argtypes = [vp, vp, vp, vp]
@@ -117,6 +122,9 @@ def load() -> ctypes.CDLL:
     lib.cf2_episode_stats_scratch_bytes.restype = ctypes.c_size_t
     lib.cf2_episode_stats_scratch_bytes.argtypes = [u32]
     lib.cf2_episode_stats.argtypes = [u32, u32] + [vp] * 10 + [ctypes.c_int, vp, vp]
+    lib.cf2_level_outcomes_scratch_bytes.restype = ctypes.c_size_t
+    lib.cf2_level_outcomes_scratch_bytes.argtypes = [u32, u32, u32]
+    lib.cf2_level_outcomes.argtypes = [u32, u32] + [vp] * 6 + [u32] + [vp] * 5 + [ctypes.c_int, vp, vp]
     lib.cf2_column_moments_scratch_bytes.restype = ctypes.c_size_t
     lib.cf2_column_moments_scratch_bytes.argtypes = [ctypes.c_uint64, u32]
     lib.cf2_column_moments.argtypes = [vp, ctypes.c_uint64, u32, vp, vp, vp]
@@ -175,7 +183,7 @@ def load() -> ctypes.CDLL:
                         "cf2_policy_weights_count", "cf2_policy_packed_count", "cf2_obs_packed_words",
                         "cf2_xchg_send_words", "cf2_xchg_recv_words", "cf2_episode_stats_scratch_bytes",
                         "cf2_column_moments_scratch_bytes", "cf2_ppo_scratch_bytes", "cf2_ppo_partial_doubles",
-                        "cf2_hj_model_sizeof"):
+                        "cf2_hj_model_sizeof", "cf2_level_outcomes_scratch_bytes"):
             getattr(lib, name).restype = ctypes.c_int
     if lib.cf2_config_sizeof() != ctypes.sizeof(CF2Config):
         raise CF2Error(f"cf2_config size mismatch: C {lib.cf2_config_sizeof()} vs Python {ctypes.sizeof(CF2Config)}")

@@ -250,6 +250,22 @@ def boltzmann_table(low=0.0, high=2.1, accuracy=0.1):
     return values, cdf
 
 
+def level_cdf_from(p):
+    """The CDF cf2_set_level_distribution builds from level weights p, in its arithmetic (that of
+    ``boltzmann_table``: cdf = cumsum(p); cdf /= cdf[-1], sequential double adds): a list of floats.
+    ValueError for a negative or non-finite weight or a sum that is not positive and finite."""
+    acc, cdf = 0.0, []
+    for x in p:
+        x = float(x)
+        if not (x >= 0.0) or math.isinf(x):
+            raise ValueError(f"level weights must be finite and non-negative, got {x}")
+        acc += x
+        cdf.append(acc)
+    if not cdf or not (acc > 0.0) or math.isinf(acc):
+        raise ValueError("level weights must have a positive, finite sum")
+    return [c / acc for c in cdf]
+
+
 def hj_grid():
     """Grid(...) of distur_gener.py:179 with GridProcessing.Grid.__init__ (:6-49) semantics."""
     gmin = np.array([-math.pi / 2.4, -math.pi / 2.4, -math.pi / 2.4, -math.pi, -math.pi, -math.pi])

@@ -630,6 +630,201 @@ class EpisodeStats:
         return out
 
 
+class LevelOutcomes:
+    """Episode outcomes per disturbance level: ``EpisodeStats`` with the finished episodes binned by
+    the level they ran under and split into crashes and time-outs (cf2_level_outcomes,
+    csrc/cf2sim_outcomes.hip; row layout in include/cf2sim.h) -- the reference's episodic_data.csv
+    (episode, disturbance level, steps, return) and per-level evaluation (utils/evaluation.py) for
+    envs that auto-reset on the device.  It owns the per-env carries, the [L + 1, 16] table (row L:
+    episodes whose level is none of ``level_values``), the scratch and an optional per-env quota.
+    Pass one to ``collect(..., outcomes=)`` every epoch, or feed ``update`` yourself, and read
+    ``summary()``.  ``set_quota(E)`` makes it count exactly E episodes of every env (``evaluate``)."""
+
+    def __init__(self, num_envs: int, device, level_values):
+        import numpy as np
+        from . import _native
+        self.lib = _native.load()
+        self.num_envs = int(num_envs)
+        if self.num_envs <= 0:
+            raise ValueError(f"num_envs must be positive, got {num_envs}")
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        lv = np.asarray(level_values, dtype=np.float64).reshape(-1).astype(np.float32)   # the cast of cf2sim_api.cpp
+        if not 1 <= lv.size <= 32:
+            raise ValueError(f"between 1 and 32 level values, got {lv.size}")
+        self.level_values = lv
+        self.num_levels = int(lv.size)
+        n, dev = self.num_envs, self.device
+        self._levels_dev = torch.from_numpy(lv.copy()).to(dev)
+        self.ep_ret = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.ep_cost = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.ep_len = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.episodes_left = None             # [N] int32 once set_quota(E) was called
+        self._table = torch.zeros(self.num_levels + 1, 16, dtype=torch.float64, device=dev)
+        self._scratch = None
+        self._all_costs = True                # every update since the last clear was given costs
+
+    @staticmethod
+    def default_level_values(cfg):
+        """The levels an env of configuration ``cfg`` can report: ``cfg.level_values[:num_levels]`` for
+        Boltzmann-level envs, ``[cfg.dstb_level]`` otherwise."""
+        if int(cfg.level_mode) == 1:
+            return [float(cfg.level_values[k]) for k in range(int(cfg.num_levels))]
+        return [float(cfg.dstb_level)]
+
+    @classmethod
+    def for_env(cls, envs) -> "LevelOutcomes":
+        return cls(envs.num_envs, envs.device, cls.default_level_values(envs.cfg))
+
+    def reset(self, mask: torch.Tensor | None = None) -> None:
+        """Forget the running episodes of all envs, or of the masked ones ([N] bool / uint8): call
+        it after an ``envs.reset(...)`` that abandons them.  The table and the quota are kept."""
+        if mask is None:
+            self.ep_ret.zero_(); self.ep_cost.zero_(); self.ep_len.zero_()
+            return
+        m = torch.as_tensor(mask).to(device=self.device).bool()
+        if tuple(m.shape) != (self.num_envs,):
+            raise ValueError(f"mask must have shape ({self.num_envs},), got {tuple(m.shape)}")
+        self.ep_ret.masked_fill_(m, 0.0); self.ep_cost.masked_fill_(m, 0.0); self.ep_len.masked_fill_(m, 0)
+
+    def set_quota(self, episodes_per_env: int | None) -> None:
+        """Record at most ``episodes_per_env`` further episodes of every env (None: no limit).  With
+        auto-resetting envs a crashing env finishes more episodes than a surviving one; a quota keeps
+        an evaluation from weighting the short episodes more."""
+        if episodes_per_env is None:
+            self.episodes_left = None
+            return
+        if int(episodes_per_env) < 0:
+            raise ValueError(f"episodes_per_env must not be negative, got {episodes_per_env}")
+        self.episodes_left = torch.full((self.num_envs,), int(episodes_per_env), dtype=torch.int32, device=self.device)
+
+    def remaining(self) -> int:
+        """Episodes the quota still waits for, over all envs (one host read; 0 without a quota)."""
+        return 0 if self.episodes_left is None else int(self.episodes_left.sum().item())
+
+    @torch.no_grad()
+    def update(self, rew: torch.Tensor, done: torch.Tensor, trunc: torch.Tensor | None = None,
+               cost: torch.Tensor | None = None, level: torch.Tensor | None = None) -> None:
+        """Scan [T, N] (or [N]: one step) rewards, done and truncation flags (uint8 or bool), costs
+        and levels forward in time and add the episodes that finished to the table.  Without
+        ``trunc`` no crash or time-out is counted, without ``level`` every episode goes to row 0."""
+        from . import _native
+        from .vec_env import _check_buf
+        if not isinstance(rew, torch.Tensor) or rew.dim() not in (1, 2):
+            raise ValueError("rew must be a [T, N] or [N] torch tensor")
+        shape = (1, self.num_envs) if rew.dim() == 1 else (rew.shape[0], self.num_envs)
+        flat = rew.dim() == 1
+        if isinstance(done, torch.Tensor) and done.dtype == torch.bool:
+            done = done.view(torch.uint8)        # same bytes (0 / 1), no copy
+        if isinstance(trunc, torch.Tensor) and trunc.dtype == torch.bool:
+            trunc = trunc.view(torch.uint8)
+        bufs = {"rew": (rew, torch.float32), "done": (done, torch.uint8), "trunc": (trunc, torch.uint8),
+                "cost": (cost, torch.float32), "level": (level, torch.float32)}
+        for name, (t, dt) in bufs.items():
+            if t is None and name in ("rew", "done"):
+                raise ValueError(f"{name} is required")
+            _check_buf(t, name, shape[1:] if flat else shape, dt, self.device, align=1 if dt == torch.uint8 else 4)
+        if shape[0] == 0:
+            return
+        need = self.lib.cf2_level_outcomes_scratch_bytes(shape[0], shape[1], self.num_levels)
+        if self._scratch is None or self._scratch.numel() * 8 < need:
+            self._scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+        _native.check(self.lib.cf2_level_outcomes(
+            shape[0], shape[1], rew.data_ptr(), _native.ptr(cost), done.data_ptr(), _native.ptr(trunc),
+            _native.ptr(level), self._levels_dev.data_ptr(), self.num_levels, self.ep_ret.data_ptr(),
+            self.ep_cost.data_ptr(), self.ep_len.data_ptr(), _native.ptr(self.episodes_left), self._table.data_ptr(), 1,
+            self._scratch.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream), "cf2_level_outcomes")
+        self._all_costs = self._all_costs and cost is not None
+
+    def raw(self) -> torch.Tensor:
+        """The [L + 1, 16] device table (a copy): what ranks gather for ``merge_raw``."""
+        return self._table.clone()
+
+    @staticmethod
+    def _empty_row():
+        import numpy as np
+        row = np.zeros(16)
+        row[[3, 7, 11]], row[[4, 8, 12]] = np.inf, -np.inf
+        return row
+
+    @staticmethod
+    def _merge_row(out, row) -> None:
+        """row into out (16 doubles each, in place); a row with count 0 is ignored"""
+        if not row[0] > 0:
+            return
+        for j in (0, 13, 14):
+            out[j] += row[j]
+        for j in (1, 5, 9):
+            out[j] += row[j]
+            out[j + 1] += row[j + 1]
+            out[j + 2] = min(out[j + 2], row[j + 2])
+            out[j + 3] = max(out[j + 3], row[j + 3])
+
+    @staticmethod
+    def merge_raw(raws) -> torch.Tensor:
+        """Combine tables of one shape (CPU tensors or arrays [L + 1, 16], e.g. every rank's ``raw()``)
+        row by row as ``EpisodeStats.merge_raw`` combines summaries: counts and sums add, minima and
+        maxima combine, a row with count 0 is ignored."""
+        import numpy as np
+        out = None
+        for r in raws:
+            r = np.asarray(r.detach().cpu() if isinstance(r, torch.Tensor) else r, dtype=np.float64)
+            if r.ndim != 2 or r.shape[1] != 16 or r.shape[0] < 2:
+                raise ValueError(f"a raw table is [L + 1, 16], got {r.shape}")
+            if out is None:
+                out = np.stack([LevelOutcomes._empty_row() for _ in range(r.shape[0])])
+            if r.shape != out.shape:
+                raise ValueError(f"tables of different shapes: {r.shape} and {out.shape}")
+            for k in range(r.shape[0]):
+                LevelOutcomes._merge_row(out[k], r[k])
+        if out is None:
+            raise ValueError("no table to merge")
+        return torch.from_numpy(out)
+
+    @staticmethod
+    def _entry(row, with_costs: bool) -> dict:
+        e = EpisodeStats.summary_of(row, with_costs=with_costs)
+        n = e["episodes"]
+        crashes, timeouts = (int(row[13]), int(row[14])) if n else (0, 0)
+        out = {"episodes": n, "crashes": crashes, "timeouts": timeouts,
+               "crash_rate": crashes / n if n else math.nan}
+        out.update({k: v for k, v in e.items() if k != "episodes"})
+        return out
+
+    @staticmethod
+    def table_of(raw, level_values, with_costs: bool = True) -> dict:
+        """The log entries of a raw table: ``{"levels": [...], "other": ..., "total": ...}``, each entry
+        ``{"episodes", "crashes", "timeouts", "crash_rate", "EpRet": {mean, std, min, max}, "EpLen",
+        "EpCosts"}`` (the population std, NaN mean / std / crash_rate with no episode); the per-level
+        ones also carry ``"level"``.  "total" merges every row, "other" included."""
+        import numpy as np
+        r = np.asarray(raw.detach().cpu() if isinstance(raw, torch.Tensor) else raw, dtype=np.float64)
+        lv = np.asarray(level_values, dtype=np.float32).reshape(-1)
+        if r.shape != (lv.size + 1, 16):
+            raise ValueError(f"a raw table for {lv.size} levels is [{lv.size + 1}, 16], got {r.shape}")
+        levels = []
+        for k in range(lv.size):
+            e = {"level": float(lv[k])}
+            e.update(LevelOutcomes._entry(r[k], with_costs))
+            levels.append(e)
+        total = LevelOutcomes._empty_row()
+        for row in r:
+            LevelOutcomes._merge_row(total, row)
+        return {"levels": levels, "other": LevelOutcomes._entry(r[lv.size], with_costs),
+                "total": LevelOutcomes._entry(total, with_costs)}
+
+    def summary(self, clear: bool = True) -> dict:
+        """Synchronise and return ``table_of`` the episodes recorded since the last clear (episodes
+        still running are not counted).  ``EpCosts`` is present only if every update since then was
+        given costs.  clear=True empties the table; the carries and the quota stay."""
+        out = self.table_of(self._table.cpu(), self.level_values, with_costs=self._all_costs)
+        if clear:
+            self._table.zero_()
+            self._all_costs = True
+        return out
+
+
 @dataclasses.dataclass
 class Rollout:
     obs: torch.Tensor        # [T, N, obs_dim]
@@ -647,6 +842,14 @@ class Rollout:
     discounted_ret: torch.Tensor  # [T, N] per-episode discounted returns (return statistics)
     # the fused path's buffers, re-used by collect(..., out=this rollout)
     storage: dict | None = dataclasses.field(default=None, repr=False, compare=False)
+    # with collect(..., outcomes=): the env-steps' info['cost'] and disturbance levels, [T, N], else
+    # None.  Init-only variables kept as plain attributes: code that walks dataclasses.fields() to
+    # move or cast a rollout's tensors sees the tensors it always saw.
+    cost: dataclasses.InitVar[torch.Tensor | None] = None
+    level: dataclasses.InitVar[torch.Tensor | None] = None
+
+    def __post_init__(self, cost, level):
+        self.cost, self.level = cost, level
 
 
 def _fused_storage(steps: int, n: int, d: int, dev) -> dict:
@@ -664,7 +867,8 @@ def _fused_storage(steps: int, n: int, d: int, dev) -> dict:
 @torch.no_grad()
 def collect(envs, ac, steps: int, obs: torch.Tensor | None = None, gamma: float = 0.99,
             lam: float = 0.95, generator: torch.Generator | None = None, fuse: bool | str = True,
-            out: Rollout | None = None, stats: EpisodeStats | None = None) -> Rollout:
+            out: Rollout | None = None, stats: EpisodeStats | None = None,
+            outcomes: "LevelOutcomes | None" = None) -> Rollout:
     """``roll_out`` for all envs of a BatchedCrazyflieEnv at once; everything stays on the GPU.
     ``ac`` is an MLPActorCritic (torch layers) or a FusedActorCritic (HIP kernels).  With a
     FusedActorCritic, ``fuse`` picks how the loop's env-steps and policy calls are launched where
@@ -677,7 +881,12 @@ def collect(envs, ac, steps: int, obs: torch.Tensor | None = None, gamma: float 
     allowed), as a training loop collecting every epoch would.
     ``stats``: an EpisodeStats that follows the envs' episodes through this collect (reset with
     the envs when ``obs`` is None, then updated from the rollout's rewards and done flags; the
-    torch-module path also hands it the per-step costs, the fused kernels write none).
+    torch-module path also hands it the per-step costs, and so does the fused path when
+    ``outcomes`` is given).
+    ``outcomes``: a LevelOutcomes that follows the episodes likewise, per disturbance level.  Only
+    then do the env-steps also write their cost and level ([T, N], ``Rollout.cost`` / ``.level``; on
+    the fused path slabs of the storage, through cf2_collect_step_info / cf2_collect_rollout_info);
+    every other output is what it is without it, bit for bit.
     ``envs`` must have been created with want_final_obs=True (time-out bootstrapping)."""
     if envs.final_obs is None:
         raise ValueError("collect() needs BatchedCrazyflieEnv(..., want_final_obs=True)")
@@ -685,6 +894,8 @@ def collect(envs, ac, steps: int, obs: torch.Tensor | None = None, gamma: float 
     o = envs.reset() if obs is None else obs
     if stats is not None and obs is None:
         stats.reset()
+    if outcomes is not None and obs is None:
+        outcomes.reset()
     fused = isinstance(ac, FusedActorCritic)
     module = ac.ac if fused else ac
     rew_den = module.ret_oms.std_host() + module.ret_oms.eps if module.ret_oms is not None else None
@@ -696,6 +907,13 @@ def collect(envs, ac, steps: int, obs: torch.Tensor | None = None, gamma: float 
         obs_buf, fin, act_all, buf_r, val_all, lp_all = S["obs"], S["fin"], S["act"], S["rew"], S["val"], S["logp"]
         buf_a, buf_v, buf_lp, last_val = act_all[:steps], val_all[:steps], lp_all[:steps], val_all[steps]
         d8, tr8, trunc_val = S["d8"], S["tr8"], S["trunc_val"]
+        buf_c = buf_l = None
+        info_kw = {}
+        if outcomes is not None:
+            if "cost" not in S:
+                S["cost"], S["level"] = torch.empty(steps, n, device=dev), torch.empty(steps, n, device=dev)
+            buf_c, buf_l = S["cost"], S["level"]
+            info_kw = {"cost_out": buf_c, "level_out": buf_l}
         obs_buf[0].copy_(o)
         trunc_val.zero_()                 # read only where truncated; zero elsewhere, as the torch path
         # the policy of step t + 1 runs right behind the env-step of step t (fused: in its launch);
@@ -703,14 +921,15 @@ def collect(envs, ac, steps: int, obs: torch.Tensor | None = None, gamma: float 
         roff = int(envs.cfg.env_id_offset)    # sampling noise keyed by the global env id
         ac.step_into(obs_buf[0], act_all[0], val_all[0], lp_all[0], row_offset=roff)
         if fuse is True and not envs.collect_rollout_into(act_all, obs_buf[1:], buf_r, d8, tr8, fin, ac, val_all,
-                                                          lp_all):
+                                                          lp_all, **info_kw):
             fuse = False                       # no fused instance for this config: two launches per step
         for t in range(steps if fuse is True else 0, steps):
             nxt = (act_all[t + 1], val_all[t + 1], lp_all[t + 1])
             if fuse and t == 0:
                 # the first step goes through every buffer check; the later slabs have the same
                 # shapes, so the loop then passes raw pointers (slab strides) to keep ahead of the GPU
-                if envs.collect_step_into(buf_a[0], obs_buf[1], buf_r[0], d8[0], tr8[0], fin[0], ac, *nxt):
+                if envs.collect_step_into(buf_a[0], obs_buf[1], buf_r[0], d8[0], tr8[0], fin[0], ac, *nxt,
+                                          **{k: v[0] for k, v in info_kw.items()}):
                     continue
                 fuse = False
             elif fuse:
@@ -718,14 +937,18 @@ def collect(envs, ac, steps: int, obs: torch.Tensor | None = None, gamma: float 
                 a_p, o_p, r_p, v_p, l_p, f_p = (buf_a.data_ptr(), obs_buf.data_ptr(), buf_r.data_ptr(),
                                                 buf_v.data_ptr(), buf_lp.data_ptr(), fin.data_ptr())
                 dp, tp = d8.data_ptr(), tr8.data_ptr()
+                c_p, lv_p = (buf_c.data_ptr(), buf_l.data_ptr()) if outcomes is not None else (None, None)
                 for u in range(t, steps):
                     nx = (a_p + (u + 1) * sa, v_p + (u + 1) * sf, l_p + (u + 1) * sf)
+                    if outcomes is not None:
+                        nx += (c_p + u * sf, lv_p + u * sf)
                     if not envs.collect_step_raw(a_p + u * sa, o_p + (u + 1) * so, r_p + u * sf, dp + u * n, tp + u * n,
                                                  f_p + u * so, ac, *nx):
                         raise RuntimeError("cf2_collect_step stopped being supported inside a collect")
                 envs._obs_latest = obs_buf[steps]    # what save_checkpoint saves after this collect
                 break
-            envs.step_into(buf_a[t], obs_buf[t + 1], buf_r[t], d8[t], tr8[t], final_obs_out=fin[t])
+            envs.step_into(buf_a[t], obs_buf[t + 1], buf_r[t], d8[t], tr8[t], final_obs_out=fin[t],
+                           **{k: v[t] for k, v in info_kw.items()})
             ac.step_into(obs_buf[t + 1], *nxt, row_offset=roff)
         per = max(1, (2**31 - 1) // n)                      # row counts of the C ABI are 32-bit
         for t0 in range(0, steps, per):                      # V(final obs) of the time-outs only
@@ -737,9 +960,11 @@ def collect(envs, ac, steps: int, obs: torch.Tensor | None = None, gamma: float 
                                     out=(S["adv"], S["ret"], S["disc"]))
         buf_o, buf_d, buf_tr = obs_buf[:steps], d8.view(torch.bool), tr8.view(torch.bool)   # 0/1 bytes
         if stats is not None:
-            stats.update(buf_r, d8)           # no cost: cf2_collect_step has no cost output
+            stats.update(buf_r, d8, buf_c)    # costs only with outcomes=: cf2_collect_step writes none
+        if outcomes is not None:
+            outcomes.update(buf_r, d8, tr8, buf_c, buf_l)
         return Rollout(buf_o, buf_a, buf_r, buf_v, buf_lp, buf_d, buf_tr, adv, ret, o, last_val, trunc_val, disc,
-                       storage=S)
+                       storage=S, cost=buf_c, level=buf_l)
     buf_o = torch.empty(steps, n, d, device=dev)
     buf_a = torch.empty(steps, n, 4, device=dev)
     buf_r = torch.empty(steps, n, device=dev)
@@ -748,7 +973,8 @@ def collect(envs, ac, steps: int, obs: torch.Tensor | None = None, gamma: float 
     buf_d = torch.empty(steps, n, dtype=torch.bool, device=dev)
     buf_tr = torch.empty(steps, n, dtype=torch.bool, device=dev)
     trunc_val = torch.zeros(steps, n, device=dev)
-    buf_c = torch.empty(steps, n, device=dev) if stats is not None else None
+    buf_c = torch.empty(steps, n, device=dev) if stats is not None or outcomes is not None else None
+    buf_l = torch.empty(steps, n, device=dev) if outcomes is not None else None
     for t in range(steps):
         a, v, lp = ac.step(o, generator=generator)
         buf_o[t] = o
@@ -761,13 +987,18 @@ def collect(envs, ac, steps: int, obs: torch.Tensor | None = None, gamma: float 
         buf_tr[t] = info["truncated"].bool()
         if buf_c is not None:
             buf_c[t] = info["cost"]
+        if buf_l is not None:
+            buf_l[t] = info["disturbance_level"]
         trunc_val[t] = ac.value(info["final_obs"])      # only read where truncated
     last_val = ac.value(o)
     adv, ret, disc = gae(buf_r, buf_v, buf_d, buf_tr, last_val, trunc_val, gamma, lam, rew_den, True)
     if stats is not None:
         stats.update(buf_r, buf_d, buf_c)
-    return Rollout(buf_o, buf_a, buf_r, buf_v, buf_lp, buf_d, buf_tr, adv, ret, o, last_val, trunc_val, disc)
+    if outcomes is not None:
+        outcomes.update(buf_r, buf_d, buf_tr, buf_c, buf_l)
+    return Rollout(buf_o, buf_a, buf_r, buf_v, buf_lp, buf_d, buf_tr, adv, ret, o, last_val, trunc_val, disc,
+                   cost=buf_c if outcomes is not None else None, level=buf_l)
 
 
 __all__ = ["OnlineMeanStd", "MLPActorCritic", "FusedActorCritic", "pack_policy_weights", "unpack_policy_weights", "gae", "gae_device", "collect",
-           "Rollout", "update_running_statistics", "EpisodeStats"]
+           "Rollout", "update_running_statistics", "EpisodeStats", "LevelOutcomes"]

@@ -195,6 +195,22 @@ class BatchedCrazyflieEnv:
         V, table_of_level = load_value_tables(source, self.cfg)
         self.bind_hj_tables(torch.from_numpy(V), table_of_level)
 
+    # ---- level curriculum ----
+    def set_level_distribution(self, p):
+        """Draw the per-episode disturbance level from weights p (one per level of cfg.level_values,
+        non-negative, not all zero; cf2_set_level_distribution) instead of the reference's fixed
+        Boltzmann() weights: the hook of a curriculum over the levels.  From the next reset on; running
+        episodes keep their level.  self.cfg.level_cdf follows, so a checkpoint carries the distribution.
+        Boltzmann-level envs only (CF2Error otherwise).  Waits for the device."""
+        from .config import level_cdf_from
+        p = [float(x) for x in (p.detach().cpu().reshape(-1).tolist() if isinstance(p, torch.Tensor)
+                                else np.asarray(p, dtype=np.float64).reshape(-1).tolist())]
+        arr = (ctypes.c_double * len(p))(*p)
+        with torch.cuda.device(self.device):
+            _native.check(self.lib.cf2_set_level_distribution(self._ctx, arr, len(p)), "cf2_set_level_distribution")
+        for k, v in enumerate(level_cdf_from(p)):
+            self.cfg.level_cdf[k] = v
+
     # ---- gym-like API ----
     def reset(self, mask: torch.Tensor | None = None) -> torch.Tensor:
         m = None
@@ -251,8 +267,9 @@ class BatchedCrazyflieEnv:
 
     def step_into(self, actions: torch.Tensor, obs_out: torch.Tensor, rew_out: torch.Tensor, done_out: torch.Tensor,
                   trunc_out: torch.Tensor | None = None, cost_out: torch.Tensor | None = None,
-                  final_obs_out: torch.Tensor | None = None):
+                  final_obs_out: torch.Tensor | None = None, level_out: torch.Tensor | None = None):
         """step() writing straight into caller buffers (rollout storage); done/trunc are uint8.
+        level_out [N] float32: the disturbance level of the finished step (info['disturbance_level']).
         Every buffer is checked (device, dtype, shape, contiguity, alignment): the kernel trusts them."""
         n, od, dev = self.num_envs, self.obs_dim, self.device
         _check_buf(actions, "actions", (n, 4), torch.float32, dev, 16)
@@ -261,22 +278,26 @@ class BatchedCrazyflieEnv:
         _check_buf(done_out, "done_out", (n,), torch.uint8, dev, 1)
         _check_buf(trunc_out, "trunc_out", (n,), torch.uint8, dev, 1)
         _check_buf(cost_out, "cost_out", (n,), torch.float32, dev)
+        _check_buf(level_out, "level_out", (n,), torch.float32, dev)
         _check_buf(final_obs_out, "final_obs_out", (n, od), torch.float32, dev, 8)
         if self.cfg.disturbance == DSTB_EXTERNAL:
             raise ValueError("this env takes an external disturbance tensor: use step(actions, dstb)")
         _native.check(self.lib.cf2_step(
             self._ctx, actions.data_ptr(), None, obs_out.data_ptr(), rew_out.data_ptr(), done_out.data_ptr(),
-            _native.ptr(trunc_out), _native.ptr(cost_out), None, _native.ptr(final_obs_out), self.stream), "cf2_step")
+            _native.ptr(trunc_out), _native.ptr(cost_out), _native.ptr(level_out), _native.ptr(final_obs_out),
+            self.stream), "cf2_step")
         self._state_version += 1
         self._obs_latest = obs_out
 
     def collect_step_into(self, actions: torch.Tensor, obs_out: torch.Tensor, rew_out: torch.Tensor,
                           done_out: torch.Tensor, trunc_out: torch.Tensor | None, final_obs_out: torch.Tensor | None,
-                          policy, act_out: torch.Tensor, val_out: torch.Tensor, logp_out: torch.Tensor) -> bool:
+                          policy, act_out: torch.Tensor, val_out: torch.Tensor, logp_out: torch.Tensor,
+                          cost_out: torch.Tensor | None = None, level_out: torch.Tensor | None = None) -> bool:
         """step_into() followed by policy.step_into(obs_out, act_out, val_out, logp_out) in one launch
         (cf2_collect_step: the collect loop's env.step + ac.step, algs/iwpg/iwpg.py:377-380).  The
         outputs are bit-identical to the two calls.  Returns False, having launched nothing, where
-        no fused instance is built (cf2sim.h); the caller then makes the two calls."""
+        no fused instance is built (cf2sim.h); the caller then makes the two calls.
+        cost_out / level_out [N] float32: step_into's outputs of those names (cf2_collect_step_info)."""
         n, od, dev = self.num_envs, self.obs_dim, self.device
         _check_buf(actions, "actions", (n, 4), torch.float32, dev, 16)
         _check_buf(obs_out, "obs_out", (n, od), torch.float32, dev, 8)    # a slab of [K, N, D] storage, N odd
@@ -287,15 +308,20 @@ class BatchedCrazyflieEnv:
         _check_buf(act_out, "act_out", (n, 4), torch.float32, dev, 16)
         _check_buf(val_out, "val_out", (n,), torch.float32, dev)
         _check_buf(logp_out, "logp_out", (n,), torch.float32, dev)
+        _check_buf(cost_out, "cost_out", (n,), torch.float32, dev)
+        _check_buf(level_out, "level_out", (n,), torch.float32, dev)
         if self.cfg.disturbance == DSTB_EXTERNAL:
             raise ValueError("this env takes an external disturbance tensor: use step(actions, dstb)")
         if policy.obs_dim != od:
             raise ValueError(f"policy obs_dim {policy.obs_dim} != env obs_dim {od}")
-        st = self.lib.cf2_collect_step(
-            self._ctx, actions.data_ptr(), obs_out.data_ptr(), rew_out.data_ptr(), done_out.data_ptr(),
-            _native.ptr(trunc_out), _native.ptr(final_obs_out), policy.w.data_ptr(), od, policy.prec, policy.seed,
-            policy.counter & 0xFFFFFFFF, int(self.cfg.env_id_offset), act_out.data_ptr(), val_out.data_ptr(),
-            logp_out.data_ptr(), self.stream)
+        args = (self._ctx, actions.data_ptr(), obs_out.data_ptr(), rew_out.data_ptr(), done_out.data_ptr(),
+                _native.ptr(trunc_out), _native.ptr(final_obs_out), policy.w.data_ptr(), od, policy.prec, policy.seed,
+                policy.counter & 0xFFFFFFFF, int(self.cfg.env_id_offset), act_out.data_ptr(), val_out.data_ptr(),
+                logp_out.data_ptr())
+        if cost_out is None and level_out is None:
+            st = self.lib.cf2_collect_step(*args, self.stream)
+        else:
+            st = self.lib.cf2_collect_step_info(*args, _native.ptr(cost_out), _native.ptr(level_out), self.stream)
         if st == _native.CF2_ERR_UNSUPPORTED:
             return False
         _native.check(st, "cf2_collect_step")
@@ -305,13 +331,20 @@ class BatchedCrazyflieEnv:
         return True
 
     def collect_step_raw(self, act: int, obs: int, rew: int, done: int, trunc: int, final_obs: int, policy,
-                         act_out: int, val_out: int, logp_out: int) -> bool:
+                         act_out: int, val_out: int, logp_out: int, cost: int | None = None,
+                         level: int | None = None) -> bool:
         """collect_step_into on raw device pointers (rollout.collect's loop after its first step,
         whose slabs collect_step_into has checked; the C ABI still rejects null or misaligned
         pointers): keeps the host's per-step cost well under the kernel's."""
-        st = self.lib.cf2_collect_step(self._ctx, act, obs, rew, done, trunc, final_obs, policy.w_ptr, self.obs_dim,
-                                       policy.prec, policy.seed, policy.counter & 0xFFFFFFFF, int(self.cfg.env_id_offset),
-                                       act_out, val_out, logp_out, self.stream)
+        if cost is None and level is None:
+            st = self.lib.cf2_collect_step(self._ctx, act, obs, rew, done, trunc, final_obs, policy.w_ptr, self.obs_dim,
+                                           policy.prec, policy.seed, policy.counter & 0xFFFFFFFF,
+                                           int(self.cfg.env_id_offset), act_out, val_out, logp_out, self.stream)
+        else:
+            st = self.lib.cf2_collect_step_info(self._ctx, act, obs, rew, done, trunc, final_obs, policy.w_ptr,
+                                                self.obs_dim, policy.prec, policy.seed, policy.counter & 0xFFFFFFFF,
+                                                int(self.cfg.env_id_offset), act_out, val_out, logp_out, cost, level,
+                                                self.stream)
         if st == _native.CF2_ERR_UNSUPPORTED:
             return False
         _native.check(st, "cf2_collect_step")
@@ -322,13 +355,15 @@ class BatchedCrazyflieEnv:
 
     def collect_rollout_into(self, act: torch.Tensor, obs_out: torch.Tensor, rew_out: torch.Tensor,
                              done_out: torch.Tensor, trunc_out: torch.Tensor | None, final_obs_out: torch.Tensor | None,
-                             policy, val_out: torch.Tensor, logp_out: torch.Tensor) -> bool:
+                             policy, val_out: torch.Tensor, logp_out: torch.Tensor,
+                             cost_out: torch.Tensor | None = None, level_out: torch.Tensor | None = None) -> bool:
         """K steps of the collect loop in one launch (cf2_collect_rollout): K = obs_out.shape[0].
         act [K+1, N, 4]: slab 0 holds the first step's actions, slabs 1..K receive the policy's
         samples on the observations after steps 0..K-1, with val_out / logp_out [K+1, N] (slab 0
         untouched); obs_out [K, N, D] (slab k = the observation after step k), rew / done / trunc
-        [K, N], final_obs [K, N, D].  Bit-identical to K collect_step_into calls.  Returns False,
-        having launched nothing, where no fused instance is built."""
+        [K, N], final_obs [K, N, D]; cost_out / level_out [K, N] float32 (optional, cf2_collect_rollout_info).
+        Bit-identical to K collect_step_into calls.  Returns False, having launched nothing, where no
+        fused instance is built."""
         K = int(obs_out.shape[0])
         n, od, dev = self.num_envs, self.obs_dim, self.device
         _check_buf(act, "act", (K + 1, n, 4), torch.float32, dev, 16)
@@ -339,15 +374,19 @@ class BatchedCrazyflieEnv:
         _check_buf(final_obs_out, "final_obs_out", (K, n, od), torch.float32, dev, 8)
         _check_buf(val_out, "val_out", (K + 1, n), torch.float32, dev)
         _check_buf(logp_out, "logp_out", (K + 1, n), torch.float32, dev)
+        _check_buf(cost_out, "cost_out", (K, n), torch.float32, dev)
+        _check_buf(level_out, "level_out", (K, n), torch.float32, dev)
         if self.cfg.disturbance == DSTB_EXTERNAL:
             raise ValueError("this env takes an external disturbance tensor: use step(actions, dstb)")
         if policy.obs_dim != od:
             raise ValueError(f"policy obs_dim {policy.obs_dim} != env obs_dim {od}")
-        st = self.lib.cf2_collect_rollout(
-            self._ctx, K, act.data_ptr(), obs_out.data_ptr(), rew_out.data_ptr(), done_out.data_ptr(),
-            _native.ptr(trunc_out), _native.ptr(final_obs_out), policy.w.data_ptr(), od, policy.prec, policy.seed,
-            policy.counter & 0xFFFFFFFF, int(self.cfg.env_id_offset), val_out.data_ptr(), logp_out.data_ptr(),
-            self.stream)
+        args = (self._ctx, K, act.data_ptr(), obs_out.data_ptr(), rew_out.data_ptr(), done_out.data_ptr(),
+                _native.ptr(trunc_out), _native.ptr(final_obs_out), policy.w.data_ptr(), od, policy.prec, policy.seed,
+                policy.counter & 0xFFFFFFFF, int(self.cfg.env_id_offset), val_out.data_ptr(), logp_out.data_ptr())
+        if cost_out is None and level_out is None:
+            st = self.lib.cf2_collect_rollout(*args, self.stream)
+        else:
+            st = self.lib.cf2_collect_rollout_info(*args, _native.ptr(cost_out), _native.ptr(level_out), self.stream)
         if st == _native.CF2_ERR_UNSUPPORTED:
             return False
         _native.check(st, "cf2_collect_rollout")

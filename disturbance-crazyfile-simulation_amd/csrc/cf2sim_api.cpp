@@ -420,6 +420,36 @@ int cf2_bind_hj_tables(cf2_ctx* ctx, const float* V_dev, int num_tables, const i
     return CF2_OK;
 }
 
+int cf2_set_level_distribution(cf2_ctx* ctx, const double* p_host, int32_t count) {
+    if (!ctx || !p_host) return CF2_ERR_INVALID_ARG;
+    if (ctx->cfg.level_mode != CF2_LEVEL_BOLTZMANN) return CF2_ERR_UNSUPPORTED;
+    if (count != ctx->cfg.num_levels) return CF2_ERR_INVALID_ARG;
+    // numpy's choice(p=...) as config.boltzmann_table restates it: cdf = cumsum(p); cdf /= cdf[-1]
+    double cdf[CF2_NUM_LEVELS_MAX];
+    double acc = 0.0;
+    for (int k = 0; k < count; ++k) {
+        if (!(p_host[k] >= 0.0) || !isfinite(p_host[k])) return CF2_ERR_INVALID_ARG;
+        acc += p_host[k];
+        cdf[k] = acc;
+    }
+    if (!(acc > 0.0) || !isfinite(acc)) return CF2_ERR_INVALID_ARG;
+    for (int k = 0; k < count; ++k) cdf[k] /= acc;
+    // the draw (boltzmann_index, cf2sim_sensing.h) counts the entries k < count - 1 with cdf[k] <= u, u =
+    // u01(...) in [0, 1 - 2^-24]: level j needs cdf[j - 1] <= u < cdf[j], which a weight of 0 leaves empty
+    // (adding 0.0 and dividing by the same value give equal entries; trailing ones are acc / acc == 1 > u)
+    // reset kernels in flight on any stream may still read the table: a setup-time call, as a binding
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e);
+    // only the CDF's words: a whole-block upload would also clear the device error word
+    e = hipMemcpy(ctx->tab_dev->level_cdf, cdf, sizeof(double) * (size_t)count, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(e);
+    for (int k = 0; k < count; ++k) {
+        ctx->cfg.level_cdf[k] = cdf[k];
+        ctx->T.level_cdf[k] = cdf[k];
+    }
+    return CF2_OK;
+}
+
 int cf2_reset(cf2_ctx* ctx, const uint8_t* mask_dev, float* obs_dev, void* stream) {
     if (!ctx) return CF2_ERR_INVALID_ARG;
     const hipError_t e = launch_reset(ctx->P, ctx->sf, mask_dev, obs_dev, (hipStream_t)stream);
@@ -465,6 +495,15 @@ int cf2_collect_step(cf2_ctx* ctx, const float* act_dev, float* obs_dev, float* 
                      uint8_t* trunc_dev, float* final_obs_dev, const float* packed_dev, uint32_t obs_dim, int precision,
                      uint64_t seed, uint32_t counter, uint32_t row_offset, float* act_out_dev, float* val_out_dev,
                      float* logp_out_dev, void* stream) {
+    return cf2_collect_step_info(ctx, act_dev, obs_dev, rew_dev, done_dev, trunc_dev, final_obs_dev, packed_dev, obs_dim,
+                                 precision, seed, counter, row_offset, act_out_dev, val_out_dev, logp_out_dev, nullptr,
+                                 nullptr, stream);
+}
+
+int cf2_collect_step_info(cf2_ctx* ctx, const float* act_dev, float* obs_dev, float* rew_dev, uint8_t* done_dev,
+                          uint8_t* trunc_dev, float* final_obs_dev, const float* packed_dev, uint32_t obs_dim,
+                          int precision, uint64_t seed, uint32_t counter, uint32_t row_offset, float* act_out_dev,
+                          float* val_out_dev, float* logp_out_dev, float* cost_dev, float* level_dev, void* stream) {
     if (!ctx || !act_dev || !obs_dev || !rew_dev || !done_dev || !packed_dev || !act_out_dev || !val_out_dev ||
         !logp_out_dev)
         return CF2_ERR_INVALID_ARG;
@@ -475,10 +514,11 @@ int cf2_collect_step(cf2_ctx* ctx, const float* act_dev, float* obs_dev, float* 
         ((uintptr_t)packed_dev & 15u) != 0)
         return CF2_ERR_INVALID_ARG;
     if (final_obs_dev && ((uintptr_t)final_obs_dev & 7u) != 0) return CF2_ERR_INVALID_ARG;
+    if ((((uintptr_t)cost_dev | (uintptr_t)level_dev) & 3u) != 0) return CF2_ERR_INVALID_ARG;
     const uint32_t od = ctx->P.noise ? 34u : 42u;
     if (obs_dim != od) return CF2_ERR_INVALID_ARG;
     if (precision != CF2_POLICY_BF16X3 || od != 34u) return CF2_ERR_UNSUPPORTED;
-    StepIO io{ctx->sf, act_dev, nullptr, obs_dev, rew_dev, done_dev, trunc_dev, nullptr, nullptr, final_obs_dev};
+    StepIO io{ctx->sf, act_dev, nullptr, obs_dev, rew_dev, done_dev, trunc_dev, cost_dev, level_dev, final_obs_dev};
     PolicyIO pio{packed_dev, (uint32_t)seed, (uint32_t)(seed >> 32), counter, row_offset, act_out_dev, val_out_dev,
                  logp_out_dev};
     const hipError_t e = launch_collect(ctx->P, io, pio, (hipStream_t)stream);
@@ -490,6 +530,15 @@ int cf2_collect_rollout(cf2_ctx* ctx, int K, float* act_dev, float* obs_dev, flo
                         uint8_t* trunc_dev, float* final_obs_dev, const float* packed_dev, uint32_t obs_dim,
                         int precision, uint64_t seed, uint32_t counter, uint32_t row_offset, float* val_dev,
                         float* logp_dev, void* stream) {
+    return cf2_collect_rollout_info(ctx, K, act_dev, obs_dev, rew_dev, done_dev, trunc_dev, final_obs_dev, packed_dev,
+                                    obs_dim, precision, seed, counter, row_offset, val_dev, logp_dev, nullptr, nullptr,
+                                    stream);
+}
+
+int cf2_collect_rollout_info(cf2_ctx* ctx, int K, float* act_dev, float* obs_dev, float* rew_dev, uint8_t* done_dev,
+                             uint8_t* trunc_dev, float* final_obs_dev, const float* packed_dev, uint32_t obs_dim,
+                             int precision, uint64_t seed, uint32_t counter, uint32_t row_offset, float* val_dev,
+                             float* logp_dev, float* cost_dev, float* level_dev, void* stream) {
     if (!ctx || K < 1 || !act_dev || !obs_dev || !rew_dev || !done_dev || !packed_dev || !val_dev || !logp_dev)
         return CF2_ERR_INVALID_ARG;
     if (ctx->cfg.disturbance == CF2_DSTB_EXTERNAL || ctx->P.ground_effect) return CF2_ERR_UNSUPPORTED;
@@ -497,10 +546,11 @@ int cf2_collect_rollout(cf2_ctx* ctx, int K, float* act_dev, float* obs_dev, flo
     if (((uintptr_t)act_dev & 15u) != 0 || ((uintptr_t)obs_dev & 7u) != 0 || ((uintptr_t)packed_dev & 15u) != 0)
         return CF2_ERR_INVALID_ARG;
     if (final_obs_dev && ((uintptr_t)final_obs_dev & 7u) != 0) return CF2_ERR_INVALID_ARG;
+    if ((((uintptr_t)cost_dev | (uintptr_t)level_dev) & 3u) != 0) return CF2_ERR_INVALID_ARG;
     const uint32_t od = ctx->P.noise ? 34u : 42u;
     if (obs_dim != od) return CF2_ERR_INVALID_ARG;
     if (precision != CF2_POLICY_BF16X3 || od != 34u) return CF2_ERR_UNSUPPORTED;
-    StepIO io{ctx->sf, act_dev, nullptr, obs_dev, rew_dev, done_dev, trunc_dev, nullptr, nullptr, final_obs_dev};
+    StepIO io{ctx->sf, act_dev, nullptr, obs_dev, rew_dev, done_dev, trunc_dev, cost_dev, level_dev, final_obs_dev};
     PolicyIO pio{packed_dev, (uint32_t)seed, (uint32_t)(seed >> 32), counter, row_offset, act_dev, val_dev, logp_dev};
     const hipError_t e = launch_collect_rollout(ctx->P, io, pio, (uint32_t)K, (hipStream_t)stream);
     if (e == hipErrorNotSupported) return CF2_ERR_UNSUPPORTED;

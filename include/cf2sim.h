@@ -237,6 +237,20 @@ int  cf2_store_policy_for(const cf2_config* cfg, const char* text, uint32_t* out
 int  cf2_bind_hj_tables(cf2_ctx* ctx, const float* V_dev, int num_tables,
                         const int32_t* table_of_level /* host, num_levels entries */);
 
+/* The distribution the per-episode disturbance level is drawn from (CF2_LEVEL_BOLTZMANN contexts;
+ * CF2_ERR_UNSUPPORTED otherwise): p_host[k] >= 0 is the weight of level_values[k], count ==
+ * num_levels.  The reference fixes it to Boltzmann() (envs/utils.py:27-39) and registers its
+ * "...WithCurriculumHJAdversary" id with that same distribution; this is the hook a curriculum
+ * sets its own through.  The CDF is built as numpy's choice(p=...) builds it: cumulative sum in
+ * double, divided by its last entry; the draw is unchanged (the count of CDF entries <= u, u in
+ * [0, 1)), so a level of weight 0 is never drawn.  A wrong count, a negative or non-finite entry
+ * or a sum that is not positive and finite: CF2_ERR_INVALID_ARG, nothing changed.  The CDF goes
+ * into the context's config and only its words of the device tables are uploaded (the device
+ * error word stays).  Synchronous and device-wide, as cf2_bind_hj_tables: it waits for all work on
+ * the device first.  It takes effect from the next reset (cf2_reset or an auto-reset inside a
+ * step); running episodes keep their level. */
+int  cf2_set_level_distribution(cf2_ctx* ctx, const double* p_host, int32_t count);
+
 /* Reset envs whose mask byte is non-zero (mask_dev NULL = all), write their obs rows. */
 int  cf2_reset(cf2_ctx* ctx, const uint8_t* mask_dev, float* obs_dev, void* stream);
 
@@ -347,6 +361,20 @@ int  cf2_collect_rollout(cf2_ctx* ctx, int K, float* act_dev, float* obs_dev, fl
                          int precision, uint64_t seed, uint32_t counter, uint32_t row_offset, float* val_dev,
                          float* logp_dev, void* stream);
 
+/* cf2_collect_step / cf2_collect_rollout with the env-step's info outputs: cost_dev and level_dev
+ * ([N] for the step, [K, N] slab-major for the rollout; either may be NULL) receive what cf2_step
+ * writes there, info['cost'] of compute_info (envs/hover_free.py:138-166) and the disturbance
+ * level of the finished step (the level column of the reference's episodic_data.csv).  With both
+ * NULL the calls are the two above, which are these with NULL, NULL: same kernels, same bits. */
+int  cf2_collect_step_info(cf2_ctx* ctx, const float* act_dev, float* obs_dev, float* rew_dev, uint8_t* done_dev,
+                           uint8_t* trunc_dev, float* final_obs_dev, const float* packed_dev, uint32_t obs_dim,
+                           int precision, uint64_t seed, uint32_t counter, uint32_t row_offset, float* act_out_dev,
+                           float* val_out_dev, float* logp_out_dev, float* cost_dev, float* level_dev, void* stream);
+int  cf2_collect_rollout_info(cf2_ctx* ctx, int K, float* act_dev, float* obs_dev, float* rew_dev, uint8_t* done_dev,
+                              uint8_t* trunc_dev, float* final_obs_dev, const float* packed_dev, uint32_t obs_dim,
+                              int precision, uint64_t seed, uint32_t counter, uint32_t row_offset, float* val_dev,
+                              float* logp_dev, float* cost_dev, float* level_dev, void* stream);
+
 /* Batched GAE over [T, n] rollout buffers (algs/core.py:459-535 finish_path on every env's
  * episode slices): done/trunc uint8 (terminal -> bootstrap 0, time-out -> trunc_val), the end of
  * the buffer bootstraps last_val [n].  rew_den > 0: reward scaling, delta uses
@@ -376,6 +404,38 @@ int  cf2_episode_stats(uint32_t T, uint32_t n, const float* rew_dev, const float
                        float* carry_ret_dev, float* carry_cost_dev, int32_t* carry_len_dev, float* ep_ret_out_dev,
                        int32_t* ep_len_out_dev, float* ep_cost_out_dev, double* summary_dev, int accumulate,
                        void* scratch_dev, void* stream);
+
+/* Per-level episode outcomes over [T, n] rollout buffers: cf2_episode_stats with the finished
+ * episodes binned by the disturbance level they ran under and split into crashes and time-outs.
+ * The reference logs the level with every episode (episodic_data.csv: episode, disturbance level,
+ * steps, return, written by the logger of algs/iwpg/iwpg.py) and evaluates a policy per level
+ * (utils/evaluation.py).  The scan and the carries are cf2_episode_stats': per step t, in time
+ * order, carry_ret += rew[t], carry_cost += cost[t] (cost_dev NULL: 0), ++carry_len, plain f32 /
+ * int adds; where done[t] != 0 the episode ends including step t and the carries restart at 0, so
+ * splitting [T, n] over several calls changes no carry and no episode value.
+ * Bin: the episode goes to row k of the table where level_dev[t, env] (the level of the finished
+ * step, as cf2_step writes it) has the bits of level_values_dev[k] (the first such k), to row L
+ * ("other") where none has, and to row 0 with level_dev NULL.  1 <= L <= CF2_NUM_LEVELS_MAX.
+ * Quota: with episodes_left_dev ([n] int32) an episode that ends in env e is recorded only while
+ * episodes_left[e] > 0, and the word is then decremented; the carries restart either way.  A
+ * quota of E per env makes an evaluation count exactly E episodes of every env, however short.
+ * table_dev, [L + 1][16] doubles: words [0..12] of a row as the cf2_episode_stats summary (count;
+ * sum, sum of squares, min, max of return, length, cost), [13] crashes (done and not trunc), [14]
+ * time-outs (trunc != 0), both 0 with trunc_dev NULL, [15] 0; an empty row has count 0, min +inf,
+ * max -inf.  accumulate != 0 merges this call into each row already there (a row whose count is 0
+ * is empty whatever else it holds); 0 overwrites.  scratch_dev:
+ * cf2_level_outcomes_scratch_bytes(T, n, L) bytes (0 for arguments the call rejects or ignores),
+ * 8-byte aligned.  Three launches on `stream`; no atomics, the geometry depends on (T, n, L) only
+ * and the same input gives the same bits.  L == 0 or L > 32, a NULL required pointer (rew, done,
+ * level_values, the carries, table, scratch) or a misaligned pointer (4 bytes; 8 for table and
+ * scratch): CF2_ERR_INVALID_ARG; T == 0 or n == 0: CF2_OK, nothing launched or written.  Every
+ * error returns before anything is launched. */
+size_t cf2_level_outcomes_scratch_bytes(uint32_t T, uint32_t n, uint32_t L);
+int  cf2_level_outcomes(uint32_t T, uint32_t n, const float* rew_dev, const float* cost_dev, const uint8_t* done_dev,
+                        const uint8_t* trunc_dev, const float* level_dev, const float* level_values_dev, uint32_t L,
+                        float* carry_ret_dev, float* carry_cost_dev, int32_t* carry_len_dev,
+                        int32_t* episodes_left_dev, double* table_dev, int accumulate, void* scratch_dev,
+                        void* stream);
 
 /* Column moments of a dense row-major [rows, D] f32 matrix, 1 <= D <= 64, read once: out_dev gets
  * mean[D], then M2[D] = sum over rows of (x - mean)^2, in fp64 -- the batch moments the running
