@@ -40,7 +40,11 @@ EXPORTED_SYMBOLS = (
     "cf2_hj_model_sizeof", "cf2_hj_time_step", "cf2_hj_solve",
     "cf2_level_outcomes_scratch_bytes", "cf2_level_outcomes", "cf2_collect_step_info", "cf2_collect_rollout_info",
     "cf2_set_level_distribution",
+    "cf2_policy_forward_pop",
 )
+# declared too, but returning uint32_t: the header scan of tests/test_abi.py lists the int, size_t and
+# const char* entry points, which EXPORTED_SYMBOLS must equal (tests/test_population_cpu.py checks these)
+EXPORTED_SYMBOLS_U32 = ("cf2_policy_pop_blocks",)
 
 
 class CF2Layout(ctypes.Structure):
@@ -117,6 +121,10 @@ def load() -> ctypes.CDLL:
     lib.cf2_policy_forward.argtypes = [vp, u32, u32, ctypes.c_int, vp, ctypes.c_uint64, u32, u32, ctypes.c_int, vp, vp,
                                        vp, vp]
     lib.cf2_value_forward_masked.argtypes = [vp, u32, u32, ctypes.c_int, vp, vp, vp, vp]
+    lib.cf2_policy_forward_pop.argtypes = [vp, ctypes.c_size_t, u32, u32, u32, ctypes.c_int, vp, vp, u32, u32,
+                                           ctypes.c_int, vp, vp, vp, vp]
+    lib.cf2_policy_pop_blocks.argtypes = [u32, u32]
+    lib.cf2_policy_pop_blocks.restype = u32
     lib.cf2_gae.argtypes = [u32, u32, vp, vp, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, vp,
                             vp, vp]
     lib.cf2_episode_stats_scratch_bytes.restype = ctypes.c_size_t

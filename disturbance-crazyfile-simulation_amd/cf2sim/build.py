@@ -12,7 +12,7 @@ INC_DIR = os.path.abspath(os.path.join(PKG_DIR, "..", "..", "include"))
 LIB = os.path.join(PKG_DIR, "libcf2sim.so")
 SOURCES = ["cf2sim_kernels.hip", "cf2sim_policy.hip", "cf2sim_util.hip", "cf2sim_exchange.hip", "cf2sim_stats.hip",
            "cf2sim_ppo.hip", "cf2sim_optim.hip", "cf2sim_natgrad.hip", "cf2sim_reduce.hip", "cf2sim_hjsolve.hip",
-           "cf2sim_outcomes.hip", "cf2sim_api.cpp"]
+           "cf2sim_outcomes.hip", "cf2sim_population.hip", "cf2sim_api.cpp"]
 # every header of csrc/ is part of every object's content key: one left out would let a stale
 # library pass for up to date
 HEADERS = sorted(f for f in os.listdir(SRC_DIR) if f.endswith(".h"))
@@ -40,7 +40,8 @@ SOURCE_FLAGS = {"cf2sim_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=on"]
                 "cf2sim_natgrad.hip": ["-ffp-contract=off"],
                 "cf2sim_reduce.hip": ["-ffp-contract=off"],
                 "cf2sim_hjsolve.hip": ["-ffp-contract=off"],
-                "cf2sim_outcomes.hip": ["-ffp-contract=on"]}
+                "cf2sim_outcomes.hip": ["-ffp-contract=on"],
+                "cf2sim_population.hip": ["-fno-slp-vectorize", "-ffp-contract=on"]}
 # The policy TU contracts like the env kernels too: the fused collect kernel (cf2sim_kernels.hip)
 # runs the same policy code (cf2sim_policy.h), and with "fast" the policy kernel alone fused the
 # standardisation's product into the hi/lo split's subtraction (8 v_fma instead of v_sub), so the
@@ -55,6 +56,8 @@ SOURCE_FLAGS = {"cf2sim_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=on"]
 # The outcomes TU follows the env kernels' policy ("on"): its carries are plain f32 adds, which no
 # contraction touches, and its fp64 sums of squares may fuse v * v + s within the one expression; they
 # are compared with a NumPy restatement within the summation-order bound (tests/test_level_outcomes_gpu.py).
+# The population TU runs the policy code of cf2sim_policy.h a third time and takes exactly the policy
+# TU's flags: a member's rows are compared bit for bit with cf2_policy_forward (tests/test_population_gpu.py).
 
 
 def _hipcc() -> str:

@@ -330,6 +330,28 @@ int  cf2_policy_forward(const float* packed_dev, uint32_t n, uint32_t obs_dim, i
 int  cf2_value_forward_masked(const float* packed_dev, uint32_t n, uint32_t obs_dim, int precision,
                               const float* obs_dev, const uint8_t* mask_dev, float* val_dev, void* stream);
 
+/* cf2_policy_forward for a population of independent learners in one launch
+ * (csrc/cf2sim_population.hip).  `members` packed blocks lie packed_stride floats apart
+ * (packed_stride >= cf2_policy_packed_count(obs_dim, precision), a multiple of 4; packed_dev 16-B
+ * aligned); member m owns rows [m * rows_per_member, (m + 1) * rows_per_member) of obs_dev
+ * [members * rows_per_member, D] and of act_dev / val_dev / logp_dev, and its sampling noise is
+ * Philox keyed (seeds_dev[m], counter, row_offset + global row); seeds_dev [members] is device memory,
+ * 8-B aligned.  Member m's rows are bit for bit those of
+ *   cf2_policy_forward(packed_dev + m * packed_stride, rows_per_member, ..., obs_dev + m * rows_per_member * D,
+ *                      seeds[m], counter, row_offset + m * rows_per_member, ...).
+ * Each 512-thread block serves one member, cf2_policy_pop_blocks(members, rows_per_member) blocks per
+ * member: max(1, min(ceil(rows_per_member / 128), floor(2 CUs / members))); 0 for arguments the
+ * forward rejects or launches nothing for.  A NULL pointer other than logp_dev, a misaligned pointer
+ * (obs_dev, seeds_dev 8 bytes; act_dev, packed_dev 16), members == 0, a packed_stride below the packed
+ * count or no multiple of 4, members * rows_per_member >= 2^32 or a grid of 2^31 or more blocks:
+ * CF2_ERR_INVALID_ARG; an (obs_dim, precision) without a kernel: CF2_ERR_UNSUPPORTED;
+ * rows_per_member == 0: CF2_OK, nothing launched.  Every error returns before anything is launched. */
+int  cf2_policy_forward_pop(const float* packed_dev, size_t packed_stride, uint32_t members, uint32_t rows_per_member,
+                            uint32_t obs_dim, int precision, const float* obs_dev, const uint64_t* seeds_dev,
+                            uint32_t counter, uint32_t row_offset, int sample, float* act_dev, float* val_dev,
+                            float* logp_dev, void* stream);
+uint32_t cf2_policy_pop_blocks(uint32_t members, uint32_t rows_per_member);
+
 /* One step of the collect loop in one launch: the env-step of cf2_step (act_dev -> obs_dev, rew,
  * done, trunc, final_obs; same arguments, no disturbance tensor, no cost/level outputs), then
  * cf2_policy_forward(sample = 1) on the new observations -> act_out_dev [N,4] (16-B aligned, the
