@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "cf2_level_outcomes_scratch_bytes", "cf2_level_outcomes", "cf2_collect_step_info", "cf2_collect_rollout_info",
     "cf2_set_level_distribution",
     "cf2_policy_forward_pop",
+    "cf2_ppo_pop_scratch_bytes", "cf2_ppo_policy_grad_pop", "cf2_ppo_value_grad_pop", "cf2_adam_step_pop",
 )
 # declared too, but returning uint32_t: the header scan of tests/test_abi.py lists the int, size_t and
 # const char* entry points, which EXPORTED_SYMBOLS must equal (tests/test_population_cpu.py checks these)
@@ -142,7 +143,14 @@ def load() -> ctypes.CDLL:
     lib.cf2_ppo_value_grad.argtypes = [vp, u32, vp, vp, u32, vp, u32] + [vp] * 5
     lib.cf2_ppo_policy_grad_gated.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, u32, vp, ctypes.c_float] + [vp] * 8
     lib.cf2_adam_step.argtypes = [vp, vp, vp, vp, u32, u32, vp] + [ctypes.c_float] * 5 + [vp, vp, ctypes.c_float, vp, vp]
-    lib.cf2_ppo_fisher_vec.argtypes = [vp, u32, vp, u32, vp, u32] + [vp] * 6
+    sz = ctypes.c_size_t
+    lib.cf2_ppo_pop_scratch_bytes.restype = sz
+    lib.cf2_ppo_pop_scratch_bytes.argtypes = [u32, u32, u32]
+    lib.cf2_ppo_policy_grad_pop.argtypes = [u32, vp, sz, u32, vp, sz, vp, sz, vp, sz, vp, sz, u32, vp, sz, u32, vp, vp,
+                                            vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp]
+    lib.cf2_ppo_value_grad_pop.argtypes = [u32, vp, sz, u32, vp, sz, vp, sz, u32, vp, sz, u32, vp, sz, vp, vp, vp, vp, vp]
+    lib.cf2_adam_step_pop.argtypes = [u32, vp, vp, vp, vp, sz, u32, u32, vp, vp] + [ctypes.c_float] * 3 + [vp] * 6
+    lib.cf2_ppo_fisher_vec.argtypes =[vp, u32, vp, u32, vp, u32] + [vp] * 6
     lib.cf2_ng_cg_init.argtypes = [vp] * 5 + [u32, u32, vp, vp, vp]
     lib.cf2_ng_cg_step.argtypes = [vp] * 4 + [u32, u32, ctypes.c_float, vp, vp, vp]
     lib.cf2_ng_direction.argtypes = [vp] * 6 + [u32, u32, ctypes.c_float, ctypes.c_float, vp, vp, vp]
@@ -191,7 +199,7 @@ def load() -> ctypes.CDLL:
                         "cf2_policy_weights_count", "cf2_policy_packed_count", "cf2_obs_packed_words",
                         "cf2_xchg_send_words", "cf2_xchg_recv_words", "cf2_episode_stats_scratch_bytes",
                         "cf2_column_moments_scratch_bytes", "cf2_ppo_scratch_bytes", "cf2_ppo_partial_doubles",
-                        "cf2_hj_model_sizeof", "cf2_level_outcomes_scratch_bytes"):
+                        "cf2_hj_model_sizeof", "cf2_level_outcomes_scratch_bytes", "cf2_ppo_pop_scratch_bytes"):
             getattr(lib, name).restype = ctypes.c_int
     if lib.cf2_config_sizeof() != ctypes.sizeof(CF2Config):
         raise CF2Error(f"cf2_config size mismatch: C {lib.cf2_config_sizeof()} vs Python {ctypes.sizeof(CF2Config)}")

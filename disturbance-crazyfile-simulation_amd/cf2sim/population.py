@@ -15,15 +15,21 @@ is keyed by the global env id, so one context of P * n envs is bit for bit P con
   storage into member-major buffers ``[P, T, n, ...]`` (torch plumbing), then the single-learner
   code per member on its contiguous slice: time-out values, GAE with the member's own return
   statistics, the member's ``EpisodeStats``.
+* ``PopulationPPOUpdater``: the resident PPO update of all members as one launch sequence whose
+  length does not depend on P (cf2_ppo_policy_grad_pop, cf2_ppo_value_grad_pop, cf2_adam_step_pop),
+  reading the member-major storage in place; per-member learning rates, clip ratios, KL targets and
+  gradient-norm limits, each member stopping at its own iteration.
 
 Every member's whole training run is bit-identical to the run it has alone on
 ``BatchedCrazyflieEnv(id, n, seed=s, env_id_offset=m * n)`` with ``FusedActorCritic(ac_m, seed_m)``
-(tests/test_population_gpu.py).  Not covered: per-member weights inside the fused collect kernels,
-one-launch gradients for all members (updates run member after member), ``group=`` and formations.
+and ``ResidentPPOUpdater(ac_m, ...)`` (tests/test_population_gpu.py,
+tests/test_population_update_gpu.py).  Not covered: per-member weights inside the fused collect
+kernels, TRPO / NPG updates of a population, ``group=`` and formations.
 """
 from __future__ import annotations
 
 import dataclasses
+import math
 
 import torch
 
@@ -254,5 +260,229 @@ def collect_population(envs, pop: Population, steps: int, obs: torch.Tensor | No
     return PopulationRollout(rollouts, obs_buf[steps], storage=S)
 
 
-__all__ = ["Population", "PopulationMember", "PopulationRollout", "collect_population", "member_major",
-           "rows_per_member"]
+def per_member(value, members: int, name: str, none=None) -> list:
+    """A hyper-parameter of a population as a list of ``members`` floats: a scalar counts for every
+    member, a sequence must have one entry per member (ValueError otherwise).  ``none``: the value a
+    None (the whole argument or an entry) stands for."""
+    if value is None or not hasattr(value, "__len__"):
+        value = [value] * members
+    value = list(value)
+    if len(value) != members:
+        raise ValueError(f"{name} must be a scalar or a sequence of {members} values, got {len(value)}")
+    if none is None and any(v is None for v in value):
+        raise ValueError(f"{name} is required for every member")
+    return [float(none if v is None else v) for v in value]
+
+
+def member_stride(tensors, name: str) -> int:
+    """The member stride, in elements, of P equally shaped row buffers that are equally spaced,
+    contiguous, non-overlapping slices of one allocation (what ``collect_population`` hands out):
+    member k's buffer starts ``k * stride`` elements after member 0's.  ValueError otherwise: the
+    population kernels take one base pointer and one stride per buffer, and nothing is copied."""
+    tensors = list(tensors)
+    t0 = tensors[0]
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or t.shape != t0.shape or t.dtype != t0.dtype or t.device != t0.device \
+                or not t.is_contiguous():
+            raise ValueError(f"the members' {name} must be contiguous tensors of one shape, dtype and device")
+    if len(tensors) == 1:
+        return t0.numel()
+    es, base = t0.element_size(), t0.data_ptr()
+    step = tensors[1].data_ptr() - base
+    if step % es or step < t0.numel() * es or any(t.data_ptr() != base + k * step for k, t in enumerate(tensors)):
+        raise ValueError(f"the members' {name} are not equally spaced slices of one buffer: a PopulationPPOUpdater "
+                         "updates from the member-major storage of collect_population")
+    return step // es
+
+
+class PopulationPPOUpdater:
+    """``ResidentPPOUpdater`` for all members of a ``Population`` at once: the launch sequence of one
+    resident update, every launch serving the P members (cf2_ppo_policy_grad_pop,
+    cf2_ppo_value_grad_pop, cf2_adam_step_pop), so an update is a number of launches that does not
+    depend on P.  Member k's update is bit for bit the one
+    ``ResidentPPOUpdater(pop.acs[k], pi_lr[k], ..., fused=pop.member(k), generator=generators[k])``
+    makes on ``rollout.members[k]`` (tests/test_population_update_gpu.py).
+
+    ``pi_lr``, ``v_lr``, ``clip_ratio``, ``target_kl`` and ``max_grad_norm`` are each a scalar or a
+    sequence of P values (members are hyper-parameter settings); the iteration counts, the number of
+    mini-batches, the betas and eps are shared.  Every launch of the policy phase is gated per member
+    by the member's own control block, so the members stop at their own iterations.  ``generators``:
+    None or P torch.Generators, member k's being the one it would give its own updater (the value
+    passes' permutations are drawn per member, exactly as ``PPOUpdater.value_minibatches`` draws them,
+    all of an update's at its start).
+
+    The row buffers are the rollout's member-major storage, read in place through one base pointer
+    and one member stride per buffer.  ``update(rollout, read=False)`` never waits for the GPU;
+    ``result()`` reads the P x 6 results in one transfer.  ``state_dict()`` is a list of P entries,
+    entry k interchangeable with ``ResidentPPOUpdater.state_dict()`` of the stand-alone learner.
+    Per update and member there is still torch plumbing: packing and unpacking the flat block, the
+    advantage moments and ``sync_from_flat``."""
+
+    def __init__(self, pop: Population, pi_lr, v_lr, clip_ratio, target_kl, train_pi_iterations: int = 80,
+                 train_v_iterations: int = 5, num_mini_batches: int = 16, betas=(0.9, 0.999), eps: float = 1e-8,
+                 max_grad_norm=None, generators=None):
+        from .ppo import flat_slice
+        P = len(pop)
+        self.pi_lr, self.v_lr = per_member(pi_lr, P, "pi_lr"), per_member(v_lr, P, "v_lr")
+        self.clip_ratio, self.target_kl = per_member(clip_ratio, P, "clip_ratio"), per_member(target_kl, P, "target_kl")
+        self.max_grad_norm = per_member(max_grad_norm, P, "max_grad_norm", none=0.0)
+        if num_mini_batches < 1:
+            raise ValueError("num_mini_batches must be at least 1")
+        if any(t < 0.0 for t in self.target_kl):
+            raise ValueError("target_kl must not be negative: the first step is taken at KL = 0")
+        if any(not (lr >= 0.0 and math.isfinite(lr)) for lr in self.pi_lr + self.v_lr) \
+                or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or not eps >= 0.0:
+            raise ValueError(f"invalid Adam hyper-parameters pi_lr={pi_lr} v_lr={v_lr} betas={betas} eps={eps}")
+        if generators is not None:
+            generators = list(generators)
+            if len(generators) != P or any(not isinstance(g, torch.Generator) for g in generators):
+                raise ValueError(f"generators must be None or {P} torch.Generators, one per member")
+        dev = torch.device(pop.device)
+        if dev.type != "cuda":
+            raise ValueError("PopulationPPOUpdater needs the population on the GPU")
+        self.pop, self.generators = pop, generators
+        self.train_pi_iterations, self.train_v_iterations = int(train_pi_iterations), int(train_v_iterations)
+        self.num_mini_batches = int(num_mini_batches)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        ac = pop.acs[0]
+        self.count = flat_slice(ac, "v")[1] + 2 * pop.obs_dim
+        self.pi_slice, self.v_slice = flat_slice(ac, "pi"), flat_slice(ac, "v")
+        f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)
+        self.pi_lr_dev, self.v_lr_dev, self.clip_dev = f32(self.pi_lr), f32(self.v_lr), f32(self.clip_ratio)
+        self.target_kl_dev, self.max_grad_norm_dev = f32(self.target_kl), f32(self.max_grad_norm)
+        z = lambda *shape, dt=torch.float32: torch.zeros(*shape, dtype=dt, device=dev)
+        self.flat, self.grad = z(P, self.count), z(P, self.count)
+        # the members' DeviceAdam states, [P, ...]: whole blocks, only the slices are ever touched
+        self.opt = {w: {"exp_avg": z(P, self.count), "exp_avg_sq": z(P, self.count), "step": z(P, dt=torch.int32),
+                        "norm": z(P, dt=torch.float64)} for w in ("pi", "v")}
+        self.ctrl = z(P, 4, dt=torch.int32)
+        self.summary0, self.summary, self.summary_v, self.summary_mb = (z(P, 8, dt=torch.float64) for _ in range(4))
+        self._bufs, self._pending = None, None
+
+    def state_dict(self) -> list:
+        return [{w: {"exp_avg": s["exp_avg"][k].clone(), "exp_avg_sq": s["exp_avg_sq"][k].clone(),
+                     "step": s["step"][k:k + 1].clone()} for w, s in self.opt.items()} for k in range(len(self.pop))]
+
+    def load_state_dict(self, sd) -> None:
+        sd = list(sd)
+        if len(sd) != len(self.pop):
+            raise ValueError(f"expected {len(self.pop)} entries, one per member, got {len(sd)}")
+        for k, entry in enumerate(sd):
+            for w, s in self.opt.items():
+                s["exp_avg"][k].copy_(entry[w]["exp_avg"])
+                s["exp_avg_sq"][k].copy_(entry[w]["exp_avg_sq"])
+                s["step"][k:k + 1].copy_(entry[w]["step"])
+
+    def result(self) -> list | None:
+        """The last update's results, one dict of ``ResidentPPOUpdater.KEYS`` per member (one device
+        read); None before the first update."""
+        from .ppo import ResidentPPOUpdater
+        if self._pending is None:
+            return None
+        out = [dict(zip(ResidentPPOUpdater.KEYS, row)) for row in self._pending.tolist()]
+        for o in out:
+            o["StopIter"] = int(o["StopIter"])
+        return out
+
+    def _buffers(self, rows: int, dev):
+        key = (rows, str(dev))
+        if self._bufs is None or self._bufs["key"] != key:
+            lib, P, d = self.pop.lib, len(self.pop), self.pop.obs_dim
+            nbytes = max(lib.cf2_ppo_pop_scratch_bytes(P, rows, d), lib.cf2_column_moments_scratch_bytes(rows, 1))
+            self._bufs = {"key": key, "scratch": torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev),
+                          "idx": torch.empty(self.train_v_iterations, P, rows, dtype=torch.int32, device=dev),
+                          "mu_old": torch.empty(P, rows, 4, device=dev),
+                          "moments": torch.empty(P, 2, dtype=torch.float64, device=dev)}
+        return self._bufs
+
+    def _adam(self, which: str, kl_summary=None, ctrl=None) -> None:
+        from . import _native
+        s, (b0, b1) = self.opt[which], self.pi_slice if which == "pi" else self.v_slice
+        p = _native.ptr
+        _native.check(self.pop.lib.cf2_adam_step_pop(
+            len(self.pop), p(self.flat), p(self.grad), p(s["exp_avg"]), p(s["exp_avg_sq"]), self.count, b0, b1 - b0,
+            p(s["step"]), p(self.pi_lr_dev if which == "pi" else self.v_lr_dev), self.betas[0], self.betas[1], self.eps,
+            p(self.max_grad_norm_dev), p(s["norm"]), p(kl_summary), p(self.target_kl_dev), p(ctrl),
+            torch.cuda.current_stream(self.flat.device).cuda_stream), "cf2_adam_step_pop")
+
+    @torch.no_grad()
+    def update(self, rollout: PopulationRollout, read: bool = True):
+        from . import _native
+        from .rollout import unpack_policy_weights
+        pop, lib, p = self.pop, self.pop.lib, _native.ptr
+        P, d, dev = len(pop), pop.obs_dim, self.flat.device
+        ms = list(rollout.members)
+        if len(ms) != P:
+            raise ValueError(f"the rollout has {len(ms)} members, the population {P}")
+        obs0 = ms[0].obs
+        if obs0.dim() != 3 or obs0.shape[-1] != d or obs0.device != dev or obs0.dtype != torch.float32:
+            raise ValueError(f"a member's obs must be float32 [T, n, {d}] on {dev}, got {tuple(obs0.shape)} on {obs0.device}")
+        rows = obs0.shape[0] * obs0.shape[1]
+        if rows == 0 or rows >= 2 ** 31:
+            raise ValueError(f"a rollout of {rows} rows per member cannot be updated from in one call")
+        want = {"obs": (*obs0.shape[:2], d), "act": (*obs0.shape[:2], 4), "logp": tuple(obs0.shape[:2]),
+                "adv": tuple(obs0.shape[:2]), "ret": tuple(obs0.shape[:2])}
+        base, stride = {}, {}
+        for name, shape in want.items():
+            ts = [getattr(r, name) for r in ms]
+            if tuple(ts[0].shape) != shape or ts[0].dtype != torch.float32 or ts[0].device != dev:
+                raise ValueError(f"a member's {name} must be float32 {shape} on {dev}")
+            base[name], stride[name] = ts[0], member_stride(ts, name)
+        if stride["obs"] % 2 or stride["act"] % 4 or base["obs"].data_ptr() % 8 or base["act"].data_ptr() % 16:
+            raise ValueError("the members' obs must be 8-byte and their act 16-byte aligned")
+        B = self._buffers(rows, dev)
+        scratch, idx, mu_old, mom = B["scratch"], B["idx"], B["mu_old"], B["moments"]
+        flat, grad, ctrl, summary0, summary = self.flat, self.grad, self.ctrl, self.summary0, self.summary
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        # Every value pass's permutations, member k's drawn with generators[k] in pass order exactly as
+        # PPOUpdater.value_minibatches draws them, but all before the first launch: torch.randperm on the
+        # GPU waits for the work already enqueued (measured at 32 768 and 131 072 rows, not at 1 048 576),
+        # which between the passes would stall the host once per member and pass.
+        for v in range(self.train_v_iterations):
+            for k in range(P):
+                g = self.generators[k] if self.generators is not None else None
+                idx[v, k].copy_(torch.randperm(rows, generator=g, device=g.device if g is not None else dev))
+        for k in range(P):        # per-member plumbing, once per update
+            _native.check(lib.cf2_column_moments(ms[k].adv.data_ptr(), rows, 1, mom[k].data_ptr(), scratch.data_ptr(),
+                                                 stream), "cf2_column_moments")
+            flat[k].copy_(pack_policy_weights(pop.acs[k]))
+
+        def pol(summ, grad=None, mu_old=None, mu_out=None, gate=None):
+            _native.check(lib.cf2_ppo_policy_grad_pop(
+                P, p(flat), self.count, d, p(base["obs"]), stride["obs"], p(base["act"]), stride["act"], p(base["logp"]),
+                stride["logp"], p(base["adv"]), stride["adv"], rows, None, 0, rows, p(mom), p(self.clip_dev), p(mu_old),
+                4 * rows, p(mu_out), 4 * rows, None, 0, p(grad), p(summ), p(scratch), p(gate), stream),
+                "cf2_ppo_policy_grad_pop")
+
+        def val(summ, grad=None, idx_ptr=None, m=rows):
+            _native.check(lib.cf2_ppo_value_grad_pop(
+                P, p(flat), self.count, d, p(base["obs"]), stride["obs"], p(base["ret"]), stride["ret"], rows, idx_ptr,
+                rows, m, None, 0, p(grad), p(summ), p(scratch), None, stream), "cf2_ppo_value_grad_pop")
+
+        ctrl.zero_()
+        summary.zero_()                   # KL and ClipFrac of an update without a policy step
+        val(self.summary_v)
+        iters = self.train_pi_iterations
+        pol(summary0, mu_out=mu_old, grad=grad if iters > 0 else None)
+        if iters > 0:
+            self._adam("pi", kl_summary=summary0, ctrl=ctrl)
+            for _ in range(1, iters):
+                pol(summary, grad=grad, mu_old=mu_old, gate=ctrl)
+                self._adam("pi", kl_summary=summary, ctrl=ctrl)
+            pol(summary, mu_old=mu_old, gate=ctrl)
+        nb = min(self.num_mini_batches, rows)
+        for v in range(self.train_v_iterations):
+            for j in range(nb):           # the members' j-th pieces of pass v's permutations
+                lo, hi = (j * rows) // nb, ((j + 1) * rows) // nb
+                val(self.summary_mb, grad=grad, idx_ptr=idx[v].data_ptr() + 4 * lo, m=hi - lo)
+                self._adam("v")
+        for k in range(P):
+            unpack_policy_weights(pop.acs[k], flat[k])
+            pop.member(k).sync_from_flat(flat[k])
+        self._pending = torch.cat([summary0[:, 1:2], self.summary_v[:, 1:2], summary[:, 4:5], summary[:, 3:4],
+                                   ctrl[:, 1:2].double(), self.opt["pi"]["norm"][:, None]], dim=1)
+        return self.result() if read else None
+
+
+__all__ = ["Population", "PopulationMember", "PopulationPPOUpdater", "PopulationRollout", "collect_population",
+           "member_major", "member_stride", "per_member", "rows_per_member"]

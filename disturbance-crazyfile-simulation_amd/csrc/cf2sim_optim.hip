@@ -53,7 +53,43 @@ __device__ __forceinline__ double powu(double b, uint32_t e) {
     return r;
 }
 
-__global__ void __launch_bounds__(ADAM_BLOCK) adam_kernel(const AdamArgs a) {
+// P members in one launch (cf2_adam_step_pop; adam_kernel<true>): workgroup k is member k's
+// adam_kernel on the slice k `stride` floats further on, with its own step word, norm, KL summary and
+// control block and with lr[k], max_grad_norm[k], target_kl[k].  It is the only writer of member k's
+// words, so the argument of the header comment above holds per member.
+struct AdamPopArgs {
+    AdamArgs base;               // member 0's pointers; lr, max_grad_norm, target_kl unused
+    size_t stride;               // floats between the members' blocks
+    const float* lr;             // [P]
+    const float* max_grad_norm;  // [P] or nullptr: no clipping
+    const float* target_kl;      // [P] or nullptr: never read (no ctrl or no kl_summary)
+};
+
+// what a kernel instance is launched with and the AdamArgs its body sees; the stand-alone instance
+// reads its own kernel argument, as before (cf2sim_ppo.hip, PpoKernelArgs, has the reason)
+template <bool POP> struct AdamKernelArgs { using type = AdamArgs; };
+template <> struct AdamKernelArgs<true> { using type = AdamPopArgs; };
+__device__ __forceinline__ const AdamArgs& adam_args_of(const AdamArgs& a) { return a; }
+__device__ __forceinline__ AdamArgs adam_args_of(const AdamPopArgs& p) {
+    const uint32_t k = blockIdx.x;
+    AdamArgs a = p.base;
+    a.w += k * p.stride;
+    a.grad += k * p.stride;
+    a.m += k * p.stride;
+    a.v += k * p.stride;
+    a.step += k;
+    if (a.norm_out) a.norm_out += k;
+    if (a.kl_summary) a.kl_summary += 8u * (size_t)k;
+    if (a.ctrl) a.ctrl += 4u * (size_t)k;
+    a.lr = p.lr[k];
+    a.max_grad_norm = p.max_grad_norm ? p.max_grad_norm[k] : 0.0f;
+    a.target_kl = p.target_kl ? p.target_kl[k] : 0.0f;
+    return a;
+}
+
+template <bool POP = false>
+__global__ void __launch_bounds__(ADAM_BLOCK) adam_kernel(const typename AdamKernelArgs<POP>::type ka) {
+    const AdamArgs a = adam_args_of(ka);
     __shared__ double wsum[ADAM_WAVES];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const bool stopped = a.ctrl && a.ctrl[0] != 0u;
@@ -124,7 +160,33 @@ extern "C" int cf2_adam_step(float* weights_dev, const float* grad_dev, float* e
     if (count > ADAM_MAX_COUNT) return CF2_ERR_UNSUPPORTED;
     const AdamArgs a = {weights_dev + begin, grad_dev + begin, exp_avg_dev + begin, exp_avg_sq_dev + begin, step_dev,
                         norm_out_dev, kl_summary_dev, ctrl_dev, count, lr, beta1, beta2, eps, max_grad_norm, target_kl};
-    hipLaunchKernelGGL(adam_kernel, dim3(1), dim3(ADAM_BLOCK), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(1), dim3(ADAM_BLOCK), 0, (hipStream_t)stream, a);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? CF2_OK : hip_fail(e);
+}
+
+extern "C" int cf2_adam_step_pop(uint32_t members, float* weights_dev, const float* grad_dev, float* exp_avg_dev,
+                                 float* exp_avg_sq_dev, size_t block_stride, uint32_t begin, uint32_t count,
+                                 uint32_t* step_dev, const float* lr_dev, float beta1, float beta2, float eps,
+                                 const float* max_grad_norm_dev, double* norm_out_dev, const double* kl_summary_dev,
+                                 const float* target_kl_dev, uint32_t* ctrl_dev, void* stream) {
+    if (count == 0 || members == 0) return CF2_OK;
+    if (!weights_dev || !grad_dev || !exp_avg_dev || !exp_avg_sq_dev || !step_dev || !lr_dev ||
+        (ctrl_dev && kl_summary_dev && !target_kl_dev))
+        return CF2_ERR_INVALID_ARG;
+    if (misaligned(weights_dev, 4) || misaligned(grad_dev, 4) || misaligned(exp_avg_dev, 4) ||
+        misaligned(exp_avg_sq_dev, 4) || misaligned(step_dev, 4) || misaligned(ctrl_dev, 4) || misaligned(lr_dev, 4) ||
+        misaligned(max_grad_norm_dev, 4) || misaligned(target_kl_dev, 4) || misaligned(norm_out_dev, 8) ||
+        misaligned(kl_summary_dev, 8))
+        return CF2_ERR_INVALID_ARG;
+    if ((uint64_t)begin + (uint64_t)count > 0xFFFFFFFFull || members >= (1u << 31)) return CF2_ERR_INVALID_ARG;
+    if (count > ADAM_MAX_COUNT) return CF2_ERR_UNSUPPORTED;
+    AdamPopArgs p = {};
+    p.base = {weights_dev + begin, grad_dev + begin, exp_avg_dev + begin, exp_avg_sq_dev + begin, step_dev,
+              norm_out_dev, kl_summary_dev, ctrl_dev, count, 0.0f, beta1, beta2, eps, 0.0f, 0.0f};
+    p.stride = block_stride;
+    p.lr = lr_dev, p.max_grad_norm = max_grad_norm_dev, p.target_kl = target_kl_dev;
+    hipLaunchKernelGGL(adam_kernel<true>, dim3(members), dim3(ADAM_BLOCK), 0, (hipStream_t)stream, p);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? CF2_OK : hip_fail(e);
 }

@@ -112,10 +112,59 @@ __device__ __forceinline__ float sum_rows(float x) {
     return x;
 }
 
-template <int D, bool PI, bool GRAD>
-__global__ void __launch_bounds__(PPO_BLOCK) ppo_kernel(const PpoArgs a) {
+// P members in one launch (cf2_ppo_*_grad_pop; ppo_kernel<D, PI, GRAD, true>): `base` holds member 0's
+// pointers, member k's lie k strides (in elements) further on.  Block b serves member b / bpm as that
+// member's block b % bpm of bpm = ppo_blocks(m), the grid the member has alone, through the one kernel
+// body: the same expressions, tile loop, LDS map and reduction order, hence the same bits.  The gate
+// word of member k is gate[4 k]: a gated member's blocks return at once, the others never look at it.
+struct PpoPopArgs {
+    PpoArgs base;                // n, m shared; clip unused; part_sum, part_grad: member 0's slice of the scratch
+    const float* clip;           // [P]
+    size_t s_w, s_obs, s_act, s_logp_old, s_adv, s_idx, s_mu_old, s_mu_out, s_logp_out;
+    size_t s_scratch;            // bytes between the members' scratch slices
+    uint32_t bpm;
+};
+
+__device__ __forceinline__ PpoArgs ppo_member_args(const PpoPopArgs& p, const uint32_t k) {
+    PpoArgs a = p.base;
+    a.W += k * p.s_w;
+    a.obs += k * p.s_obs;
+    if (a.act) a.act += k * p.s_act;
+    if (a.logp_old) a.logp_old += k * p.s_logp_old;
+    a.adv += k * p.s_adv;
+    if (a.idx) a.idx += k * p.s_idx;
+    if (a.adv_moments) a.adv_moments += 2u * (size_t)k;
+    if (a.mu_old) a.mu_old += k * p.s_mu_old;
+    if (a.mu_out) a.mu_out += k * p.s_mu_out;
+    if (a.logp_out) a.logp_out += k * p.s_logp_out;
+    a.part_sum = reinterpret_cast<double*>(reinterpret_cast<char*>(a.part_sum) + k * p.s_scratch);
+    a.part_grad = reinterpret_cast<float*>(reinterpret_cast<char*>(a.part_grad) + k * p.s_scratch);
+    if (p.clip) a.clip = p.clip[k];
+    if (a.gate) a.gate += 4u * (size_t)k;
+    return a;
+}
+
+// What a kernel instance is launched with, the member's PpoArgs and the block geometry its body
+// sees.  The body stays in the __global__ function, with the stand-alone instance reading its own
+// kernel argument, blockIdx and gridDim as before: moved into a __device__ function that two kernels
+// call, the policy-gradient instances spilled (24 and 92 bytes per lane) and every instance's code
+// changed; this way the stand-alone instances' code is unchanged byte for byte.
+template <bool POP> struct PpoKernelArgs { using type = PpoArgs; };
+template <> struct PpoKernelArgs<true> { using type = PpoPopArgs; };
+__device__ __forceinline__ const PpoArgs& ppo_args_of(const PpoArgs& a) { return a; }
+__device__ __forceinline__ PpoArgs ppo_args_of(const PpoPopArgs& p) { return ppo_member_args(p, blockIdx.x / p.bpm); }
+__device__ __forceinline__ uint32_t ppo_block_of(const PpoArgs&) { return blockIdx.x; }
+__device__ __forceinline__ uint32_t ppo_block_of(const PpoPopArgs& p) { return blockIdx.x % p.bpm; }
+__device__ __forceinline__ uint32_t ppo_nblocks_of(const PpoArgs&) { return gridDim.x; }
+__device__ __forceinline__ uint32_t ppo_nblocks_of(const PpoPopArgs& p) { return p.bpm; }
+
+// POP = false: one learner, block blockIdx.x of gridDim.x.  POP = true: P members, this block being
+// block ppo_block_of(ka) of its member's ppo_nblocks_of(ka).
+template <int D, bool PI, bool GRAD, bool POP = false>
+__global__ void __launch_bounds__(PPO_BLOCK) ppo_kernel(const typename PpoKernelArgs<POP>::type ka) {
     using N = PpoNet<D, PI>;
     using L = PolicyLayout<D>;
+    const PpoArgs& a = ppo_args_of(ka);
     constexpr int H = N::H, NO = N::NO, WS = PPO_WS, AS = PPO_AS, ZS = PPO_ZS;
     if (a.gate && *a.gate != 0u) return;          // the same word for every block: this launch only reads it
     __shared__ __attribute__((aligned(16))) float lds[N::LDS_FLOATS];
@@ -200,7 +249,7 @@ __global__ void __launch_bounds__(PPO_BLOCK) ppo_kernel(const PpoArgs a) {
     }
     double S[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 
-    const uint32_t ntiles = (a.m + 15u) / 16u, nwaves = gridDim.x * PPO_WAVES;
+    const uint32_t ntiles = (a.m + 15u) / 16u, nwaves = ppo_nblocks_of(ka) * PPO_WAVES;
     // the row of position 16 tile + c; a position past m reads row m - 1 and contributes nothing
     auto row_of = [&](uint32_t tile) {
         const uint32_t jc = __builtin_elementwise_min(tile * 16u + (uint32_t)c, a.m - 1u);
@@ -217,7 +266,7 @@ __global__ void __launch_bounds__(PPO_BLOCK) ppo_kernel(const PpoArgs a) {
             xr[it] = a.obs[(size_t)__shfl(row, r) * D + k];
         }
     };
-    uint32_t tile = blockIdx.x * PPO_WAVES + wave;
+    uint32_t tile = ppo_block_of(ka) * PPO_WAVES + wave;
     uint32_t row = row_of(tile < ntiles ? tile : ntiles - 1u);
     load_obs(row);
     for (; tile < ntiles; tile += nwaves) {
@@ -449,7 +498,7 @@ __global__ void __launch_bounds__(PPO_BLOCK) ppo_kernel(const PpoArgs a) {
         double v = 0.0;
         if (tid >= 1 && tid <= 5)
             for (int w = 0; w < PPO_WAVES; ++w) v += sred[w][tid - 1];
-        a.part_sum[(size_t)blockIdx.x * PPO_SUM + tid] = v;
+        a.part_sum[(size_t)ppo_block_of(ka) * PPO_SUM + tid] = v;
     }
 
     if constexpr (GRAD) {
@@ -509,7 +558,7 @@ __global__ void __launch_bounds__(PPO_BLOCK) ppo_kernel(const PpoArgs a) {
             }
             __syncthreads();
         }
-        float* dst = a.part_grad + (size_t)blockIdx.x * N::NPAR;
+        float* dst = a.part_grad + (size_t)ppo_block_of(ka) * N::NPAR;
         for (int p = tid; p < N::NPAR; p += PPO_BLOCK) dst[p] = red[p];
     }
 }
@@ -534,6 +583,35 @@ __global__ void __launch_bounds__(256) ppo_merge_kernel(const float* __restrict_
         double acc = 0.0;
         for (uint32_t b = 0; b < blocks; ++b) acc += part_sum[(size_t)b * PPO_SUM + k];
         summary[k] = k == 0 ? (double)m : acc / (double)m;      // slots 6, 7 (and the unused ones) sum zeros
+    }
+}
+
+// ppo_merge_kernel for P members: blocks [k mblocks, (k + 1) mblocks) are member k's merge launch on
+// member k's slice of the scratch (scratch_stride bytes apart), the same sums in the same order and
+// the same single rounding, written to grad + k grad_stride (already offset to the network's slice)
+// and summary + 8 k.  gate: member k's word is gate[4 k].
+__global__ void __launch_bounds__(256) ppo_merge_pop_kernel(const float* __restrict__ part_grad,
+                                                            const double* __restrict__ part_sum, size_t scratch_stride,
+                                                            uint32_t mblocks, uint32_t blocks, uint32_t npar, uint32_t m,
+                                                            float* __restrict__ grad, size_t grad_stride,
+                                                            double* __restrict__ summary,
+                                                            const uint32_t* __restrict__ gate) {
+    const uint32_t k = blockIdx.x / mblocks, bx = blockIdx.x - k * mblocks;
+    if (gate && gate[4u * (size_t)k] != 0u) return;
+    part_grad = reinterpret_cast<const float*>(reinterpret_cast<const char*>(part_grad) + k * scratch_stride);
+    part_sum = reinterpret_cast<const double*>(reinterpret_cast<const char*>(part_sum) + k * scratch_stride);
+    const uint32_t p = bx * 256u + threadIdx.x;
+    if (grad && p < npar) {
+        double acc = 0.0;
+#pragma unroll 8
+        for (uint32_t b = 0; b < blocks; ++b) acc += (double)part_grad[(size_t)b * npar + p];
+        grad[k * grad_stride + p] = (float)(acc / (double)m);
+    }
+    if (bx == 0 && threadIdx.x < PPO_SUM) {
+        const uint32_t j = threadIdx.x;
+        double acc = 0.0;
+        for (uint32_t b = 0; b < blocks; ++b) acc += part_sum[(size_t)b * PPO_SUM + j];
+        summary[(size_t)PPO_SUM * k + j] = j == 0 ? (double)m : acc / (double)m;
     }
 }
 
@@ -601,6 +679,41 @@ static int ppo_launch(PpoArgs a, float* grad, double* summary, void* scratch, hi
 }
 
 static bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1u)) != 0; }
+
+// a member's slice of the population scratch: the stand-alone scratch, rounded up to 16 bytes
+static size_t ppo_pop_slice_bytes(uint32_t m, uint32_t D) {
+    const size_t one = (size_t)PPO_MAX_BLOCKS * PPO_SUM * sizeof(double) + (size_t)ppo_blocks(m) * ppo_npar_max(D) * sizeof(float);
+    return (one + 15u) & ~(size_t)15u;
+}
+
+// the two launches of a population call; p.base, the strides and p.clip are filled in by the caller
+template <int D, bool PI>
+static int ppo_pop_launch(PpoPopArgs p, uint32_t members, float* grad, double* summary, void* scratch, hipStream_t s) {
+    using N = PpoNet<D, PI>;
+    p.bpm = ppo_blocks(p.base.m);
+    p.s_scratch = ppo_pop_slice_bytes(p.base.m, D);
+    p.base.part_sum = static_cast<double*>(scratch);
+    p.base.part_grad = reinterpret_cast<float*>(p.base.part_sum + (size_t)PPO_MAX_BLOCKS * PPO_SUM);
+    const uint32_t grid = members * p.bpm;         // below 2^31: checked by the caller
+    if (grad)
+        hipLaunchKernelGGL((ppo_kernel<D, PI, true, true>), dim3(grid), dim3(PPO_BLOCK), 0, s, p);
+    else
+        hipLaunchKernelGGL((ppo_kernel<D, PI, false, true>), dim3(grid), dim3(PPO_BLOCK), 0, s, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e);
+    const uint32_t mblocks = grad ? (N::NPAR + 255u) / 256u : 1u;
+    hipLaunchKernelGGL(ppo_merge_pop_kernel, dim3(members * mblocks), dim3(256), 0, s, p.base.part_grad, p.base.part_sum,
+                       p.s_scratch, mblocks, p.bpm, (uint32_t)N::NPAR, p.base.m, grad ? grad + N::BASE : nullptr, p.s_w,
+                       summary, p.base.gate);
+    e = hipGetLastError();
+    return e == hipSuccess ? CF2_OK : hip_fail(e);
+}
+
+// a grid of members * blocks per member that the launch cannot take
+static bool ppo_pop_grid_overflows(uint32_t members, uint32_t m, uint32_t D) {
+    const uint32_t merge = (ppo_npar_max(D) + 255u) / 256u, grad = ppo_blocks(m);      // blocks per member, either launch
+    return (uint64_t)members * (grad > merge ? grad : merge) >= (1ull << 31);
+}
 
 // the fixed size of a rank-partial block: the head and the larger (value) slice
 template <int D>
@@ -1126,6 +1239,72 @@ extern "C" int cf2_ppo_value_grad(const float* weights_dev, uint32_t obs_dim, co
     const hipStream_t s = (hipStream_t)stream;
     return obs_dim == 34 ? ppo_launch<34, false>(a, grad_dev, summary_dev, scratch_dev, s)
                          : ppo_launch<42, false>(a, grad_dev, summary_dev, scratch_dev, s);
+}
+
+// ---- populations (include/cf2sim.h: "for a population of `members` independent learners")
+extern "C" size_t cf2_ppo_pop_scratch_bytes(uint32_t members, uint32_t m, uint32_t obs_dim) {
+    if ((obs_dim != 34 && obs_dim != 42) || members == 0) return 0;
+    return (size_t)members * ppo_pop_slice_bytes(m, obs_dim);
+}
+
+// a member stride in elements of `elem` bytes that breaks the alignment `a` of its array
+static bool stride_misaligned(size_t stride, size_t elem, size_t a) { return (stride * elem) % a != 0; }
+
+extern "C" int cf2_ppo_policy_grad_pop(uint32_t members, const float* weights_dev, size_t weights_stride, uint32_t obs_dim,
+                                       const float* obs_dev, size_t obs_stride, const float* act_dev, size_t act_stride,
+                                       const float* logp_old_dev, size_t logp_old_stride, const float* adv_dev,
+                                       size_t adv_stride, uint32_t n, const uint32_t* idx_dev, size_t idx_stride, uint32_t m,
+                                       const double* adv_moments_dev, const float* clip_ratio_dev, const float* mu_old_dev,
+                                       size_t mu_old_stride, float* mu_out_dev, size_t mu_out_stride, float* logp_out_dev,
+                                       size_t logp_out_stride, float* grad_dev, double* summary_dev, void* scratch_dev,
+                                       const uint32_t* ctrl_dev, void* stream) {
+    if (obs_dim != 34 && obs_dim != 42) return CF2_ERR_UNSUPPORTED;
+    if (m == 0 || members == 0) return CF2_OK;
+    if (!weights_dev || !obs_dev || !act_dev || !logp_old_dev || !adv_dev || !clip_ratio_dev || !summary_dev ||
+        !scratch_dev || n == 0 || (!idx_dev && m > n))
+        return CF2_ERR_INVALID_ARG;
+    if (misaligned(weights_dev, 4) || misaligned(obs_dev, 8) || misaligned(act_dev, 16) || misaligned(logp_old_dev, 4) ||
+        misaligned(adv_dev, 4) || misaligned(idx_dev, 4) || misaligned(adv_moments_dev, 8) || misaligned(clip_ratio_dev, 4) ||
+        misaligned(mu_old_dev, 4) || misaligned(mu_out_dev, 4) || misaligned(logp_out_dev, 4) || misaligned(grad_dev, 4) ||
+        misaligned(summary_dev, 8) || misaligned(scratch_dev, 8) || misaligned(ctrl_dev, 4))
+        return CF2_ERR_INVALID_ARG;
+    if (stride_misaligned(obs_stride, 4, 8) || stride_misaligned(act_stride, 4, 16)) return CF2_ERR_INVALID_ARG;
+    if (ppo_pop_grid_overflows(members, m, obs_dim)) return CF2_ERR_INVALID_ARG;
+    PpoPopArgs p = {};
+    p.base = {weights_dev, obs_dev, act_dev, logp_old_dev, adv_dev, idx_dev, adv_moments_dev, mu_old_dev, mu_out_dev,
+              logp_out_dev, nullptr, nullptr, n, m, 0.0f, ctrl_dev};
+    p.clip = clip_ratio_dev;
+    p.s_w = weights_stride, p.s_obs = obs_stride, p.s_act = act_stride, p.s_logp_old = logp_old_stride;
+    p.s_adv = adv_stride, p.s_idx = idx_stride, p.s_mu_old = mu_old_stride, p.s_mu_out = mu_out_stride;
+    p.s_logp_out = logp_out_stride;
+    const hipStream_t s = (hipStream_t)stream;
+    return obs_dim == 34 ? ppo_pop_launch<34, true>(p, members, grad_dev, summary_dev, scratch_dev, s)
+                         : ppo_pop_launch<42, true>(p, members, grad_dev, summary_dev, scratch_dev, s);
+}
+
+extern "C" int cf2_ppo_value_grad_pop(uint32_t members, const float* weights_dev, size_t weights_stride, uint32_t obs_dim,
+                                      const float* obs_dev, size_t obs_stride, const float* target_dev, size_t target_stride,
+                                      uint32_t n, const uint32_t* idx_dev, size_t idx_stride, uint32_t m, float* val_out_dev,
+                                      size_t val_out_stride, float* grad_dev, double* summary_dev, void* scratch_dev,
+                                      const uint32_t* ctrl_dev, void* stream) {
+    if (obs_dim != 34 && obs_dim != 42) return CF2_ERR_UNSUPPORTED;
+    if (m == 0 || members == 0) return CF2_OK;
+    if (!weights_dev || !obs_dev || !target_dev || !summary_dev || !scratch_dev || n == 0 || (!idx_dev && m > n))
+        return CF2_ERR_INVALID_ARG;
+    if (misaligned(weights_dev, 4) || misaligned(obs_dev, 8) || misaligned(target_dev, 4) || misaligned(idx_dev, 4) ||
+        misaligned(val_out_dev, 4) || misaligned(grad_dev, 4) || misaligned(summary_dev, 8) || misaligned(scratch_dev, 8) ||
+        misaligned(ctrl_dev, 4))
+        return CF2_ERR_INVALID_ARG;
+    if (stride_misaligned(obs_stride, 4, 8)) return CF2_ERR_INVALID_ARG;
+    if (ppo_pop_grid_overflows(members, m, obs_dim)) return CF2_ERR_INVALID_ARG;
+    PpoPopArgs p = {};
+    p.base = {weights_dev, obs_dev, nullptr, nullptr, target_dev, idx_dev, nullptr, nullptr, nullptr, val_out_dev,
+              nullptr, nullptr, n, m, 0.0f, ctrl_dev};
+    p.s_w = weights_stride, p.s_obs = obs_stride, p.s_adv = target_stride, p.s_idx = idx_stride;
+    p.s_logp_out = val_out_stride;
+    const hipStream_t s = (hipStream_t)stream;
+    return obs_dim == 34 ? ppo_pop_launch<34, false>(p, members, grad_dev, summary_dev, scratch_dev, s)
+                         : ppo_pop_launch<42, false>(p, members, grad_dev, summary_dev, scratch_dev, s);
 }
 
 extern "C" int cf2_ppo_fisher_vec(const float* weights_dev, uint32_t obs_dim, const float* obs_dev, uint32_t n,

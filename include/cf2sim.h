@@ -555,6 +555,67 @@ int  cf2_adam_step(float* weights_dev, const float* grad_dev, float* exp_avg_dev
                    float max_grad_norm, double* norm_out_dev, const double* kl_summary_dev, float target_kl,
                    uint32_t* ctrl_dev, void* stream);
 
+/* The three calls above for a population of `members` independent learners (cf2_policy_forward_pop's
+ * members), each as one launch chain whose length does not depend on `members`.  The defining
+ * property: for every k < members, member k's outputs are the bits the stand-alone call
+ * (cf2_ppo_policy_grad_gated, cf2_ppo_value_grad, cf2_adam_step) writes when given base + k * stride
+ * for every array argument, clip_ratio_dev[k] (or lr_dev[k], max_grad_norm_dev[k], target_kl_dev[k])
+ * and ctrl_dev + 4 k.  Nothing else is written: not the words between the members' slices, not the
+ * words of grad outside the network's slice.
+ * Every array argument is followed by its member stride in elements of its own type (floats, or
+ * uint32 for idx); the strides are independent of one another (in member-major rollout storage obs
+ * is [members, T + 1, n, D] and everything else [members, T, n, ...]).  A stride may be anything the
+ * member slices do not overlap under; the stride of an optional array that is NULL is ignored.
+ * Alignment: what the stand-alone call asks of a pointer holds for the base and for the stride in
+ * bytes (obs: 8, act: 16, everything else 4).  n and m are the same for every member.
+ *   weights_dev, grad_dev   [members] flat blocks weights_stride floats apart (grad_dev NULL: evaluate only)
+ *   idx_dev                 member k's m indices at idx_dev + k * idx_stride; NULL: rows 0..m-1 of every member
+ *   adv_moments_dev         [members][2] doubles (NULL: advantages as they are)
+ *   clip_ratio_dev          [members] floats, device memory
+ *   summary_dev             [members][8] doubles
+ *   ctrl_dev                [members][4] uint32 (cf2_adam_step_pop's control blocks) or NULL: ungated.
+ *                           A member whose ctrl word [4 k] is non-zero when the kernels start is
+ *                           skipped in both launches -- nothing of it is written -- and the other
+ *                           members are unaffected.  The value call takes the gate too.
+ *   scratch_dev             cf2_ppo_pop_scratch_bytes(members, m, obs_dim) bytes, 8-byte aligned:
+ *                           `members` slices of cf2_ppo_scratch_bytes(m, obs_dim) rounded up to 16
+ *                           bytes.  0 for an unsupported obs_dim or members == 0.
+ * Geometry: member k runs the blocks it runs alone, b = min(ceil(ceil(m / 16) / 4), 512) of them, as
+ * blocks [k b, (k + 1) b) of one grid of members * b; the merge launch has one grid row per member.
+ * No atomics; the same input gives the same bits.
+ * cf2_adam_step_pop: one 1 024-thread workgroup per member on the words [begin, begin + count) of
+ * member k's blocks (weights, grad, exp_avg, exp_avg_sq: block_stride floats apart); step_dev
+ * [members] uint32; norm_out_dev [members] doubles or NULL; kl_summary_dev [members][8] doubles or
+ * NULL; ctrl_dev [members][4] uint32 or NULL; lr_dev [members] floats (every value finite and >= 0:
+ * the caller's duty, the call cannot read them); max_grad_norm_dev [members] floats or NULL (no
+ * clipping); target_kl_dev [members] floats, required where ctrl_dev and kl_summary_dev are both
+ * given; beta1, beta2 and eps are shared.  Member k's workgroup is the only writer of member k's
+ * words (the stop flag among them); the gradient launches only read them.
+ * Errors, all returned before anything is launched: obs_dim not 34 or 42: CF2_ERR_UNSUPPORTED (Adam:
+ * count > 2^20); a NULL required pointer (those of the stand-alone call, clip_ratio_dev, lr_dev), a
+ * misaligned base or stride, n == 0, idx_dev == NULL with m > n, a grid of 2^31 blocks or more
+ * (members * b; Adam: members), begin + count past 32 bits: CF2_ERR_INVALID_ARG; m == 0, members == 0
+ * or count == 0: CF2_OK, nothing launched or written. */
+size_t cf2_ppo_pop_scratch_bytes(uint32_t members, uint32_t m, uint32_t obs_dim);
+int  cf2_ppo_policy_grad_pop(uint32_t members, const float* weights_dev, size_t weights_stride, uint32_t obs_dim,
+                             const float* obs_dev, size_t obs_stride, const float* act_dev, size_t act_stride,
+                             const float* logp_old_dev, size_t logp_old_stride, const float* adv_dev, size_t adv_stride,
+                             uint32_t n, const uint32_t* idx_dev, size_t idx_stride, uint32_t m,
+                             const double* adv_moments_dev, const float* clip_ratio_dev, const float* mu_old_dev,
+                             size_t mu_old_stride, float* mu_out_dev, size_t mu_out_stride, float* logp_out_dev,
+                             size_t logp_out_stride, float* grad_dev, double* summary_dev, void* scratch_dev,
+                             const uint32_t* ctrl_dev, void* stream);
+int  cf2_ppo_value_grad_pop(uint32_t members, const float* weights_dev, size_t weights_stride, uint32_t obs_dim,
+                            const float* obs_dev, size_t obs_stride, const float* target_dev, size_t target_stride,
+                            uint32_t n, const uint32_t* idx_dev, size_t idx_stride, uint32_t m, float* val_out_dev,
+                            size_t val_out_stride, float* grad_dev, double* summary_dev, void* scratch_dev,
+                            const uint32_t* ctrl_dev, void* stream);
+int  cf2_adam_step_pop(uint32_t members, float* weights_dev, const float* grad_dev, float* exp_avg_dev,
+                       float* exp_avg_sq_dev, size_t block_stride, uint32_t begin, uint32_t count, uint32_t* step_dev,
+                       const float* lr_dev, float beta1, float beta2, float eps, const float* max_grad_norm_dev,
+                       double* norm_out_dev, const double* kl_summary_dev, const float* target_kl_dev,
+                       uint32_t* ctrl_dev, void* stream);
+
 /* Fisher-vector product of the policy, out = F vec, for the natural-gradient updates (algs/npg,
  * algs/trpo: the Hessian-vector product of the mean KL to the detached policy).  The policy is
  * Gaussian with an untrained log_std, so KL = sum_k (mu_old_k - mu_k)^2 / (2 sigma_k^2) and its Hessian

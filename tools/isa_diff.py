@@ -1,7 +1,11 @@
 """Per-kernel comparison of two device assembly listings of one source (hipcc --cuda-device-only -S
 with cf2sim.build._compile_flags(src)): which kernel instances are byte-identical (function text and
-.amdhsa_* descriptor), and the resources of those that are not.
-python tools/isa_diff.py BEFORE.s AFTER.s [--label TEXT]"""
+.amdhsa_* descriptor), and the resources of those that are not.  Comments and the blanks before
+them are not compared: they carry the function's position in the listing.
+--rename PATTERN REPL (repeatable) rewrites the mangled symbols of AFTER with re.sub before they are
+matched, for an instance whose template gained a defaulted parameter: the symbol is part of its own
+text and descriptor, so it is rewritten there too.
+python tools/isa_diff.py BEFORE.s AFTER.s [--label TEXT] [--rename PATTERN REPL]..."""
 import argparse
 import re
 import shutil
@@ -11,9 +15,16 @@ RES = (("vgpr", "next_free_vgpr"), ("agpr_off", "accum_offset"), ("sgpr", "next_
        ("lds", "group_segment_fixed_size"), ("scratch", "private_segment_fixed_size"))
 
 
-def kernels(path):
+def kernels(path, renames=()):
     """{symbol: (function text, descriptor text, resources)} of every .amdhsa_kernel of the listing."""
-    lines = open(path).read().split("\n")
+    src = open(path).read()
+    for sym in sorted(set(re.findall(r"\.amdhsa_kernel\s+(\w+)", src)), key=len, reverse=True):
+        new = sym
+        for pat, repl in renames:
+            new = re.sub(pat, repl, new)
+        if new != sym:
+            src = re.sub(rf"\b{re.escape(sym)}\b", new, src)
+    lines = src.split("\n")
     start = {}
     for n, l in enumerate(lines):
         m = re.match(r"^(\w+):\s*(;.*)?$", l)
@@ -49,6 +60,11 @@ def kernels(path):
         # block labels carry the function's position in the listing, which moves with the order
         # of instantiation: not a difference of the kernel
         text = re.sub(r"\.LBB\d+_", ".LBB_", "\n".join(lines[b:f]))
+        # so do the comments ("; in Loop: Header=BB11_5") and their column
+        text = re.sub(r"[ \t]*;.*$", "", text, flags=re.M)
+        # the section a function is emitted into (.text, or a comdat group of its own for a template's
+        # instance) is no instruction either
+        text = re.sub(r"^\s*\.(text|section)\b.*$", "", text, flags=re.M)
         out[sym] = (text, "\n".join(desc), res)
         n = e + 1
     return out
@@ -67,8 +83,9 @@ def main():
     ap.add_argument("before")
     ap.add_argument("after")
     ap.add_argument("--label", default="")
+    ap.add_argument("--rename", nargs=2, action="append", default=[], metavar=("PATTERN", "REPL"))
     a = ap.parse_args()
-    A, B = kernels(a.before), kernels(a.after)
+    A, B = kernels(a.before), kernels(a.after, a.rename)
     names = demangle(sorted(set(A) | set(B)))
     same = [s for s in A if s in B and A[s][:2] == B[s][:2]]
     diff = [s for s in A if s in B and A[s][:2] != B[s][:2]]
