@@ -1317,6 +1317,9 @@ __global__ void state_convert_kernel(uint32_t N, float* __restrict__ sf, float* 
             if (to_public) pf[(size_t)f * N + i] = 1.0f - sf[slot_index(i, pub_float_slot(f + 4, noise != 0))];
             continue;
         }
+        // With sensor noise o_{k-1} has 13 entries and S_LPF lies on the slots of entries 13..15: an
+        // import takes the low-pass state from F_LPF alone, whatever the snapshot's unused entries hold.
+        if (!to_public && noise != 0 && f >= F_OBS_PREV && slot >= S_LPF && slot < S_LPF + 3) continue;
         float* in = sf + slot_index(i, slot);
         if (to_public) pf[(size_t)f * N + i] = *in;
         else *in = pf[(size_t)f * N + i];

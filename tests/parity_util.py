@@ -110,6 +110,8 @@ def state_fields(cfg):
     if cfg.disturbance in (3, 4):       # constant wind, gust: the episode's / current torque
         g["dstb"] = [100, 101, 102]
         g["level"] = [103]
+    if cfg.level_mode == 1:             # a level drawn per episode (Boltzmann)
+        g["level"] = [103]
     if cfg.use_motor_dynamics:
         g["motor_lo"] = list(range(104, 108))
     return g

@@ -6,19 +6,37 @@ import numpy as np
 import pytest
 import torch
 
+from parity_util import N1
+
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("env_id", ["DroneHoverBulletFreeEnvWithGust-v0", "DroneHoverBulletEnvWithRandomAdversary-v0"])
-def test_resume_from_checkpoint_is_bit_identical(gpu, tmp_path, env_id):
+FREE = "DroneHoverBulletFreeEnvWithoutAdversary-v0"
+# (env id, kwargs, env count, env-steps before the checkpoint, env-steps after it); the first two keep
+# their ids.  aggregate_phy_steps=1 halves the env-step, so that case runs a longer window for the
+# resets after the resume.
+RESUME_CASES = [
+    pytest.param("DroneHoverBulletFreeEnvWithGust-v0", {}, 3000, 20, 20, id="DroneHoverBulletFreeEnvWithGust-v0"),
+    pytest.param("DroneHoverBulletEnvWithRandomAdversary-v0", {}, 3000, 20, 20,
+                 id="DroneHoverBulletEnvWithRandomAdversary-v0"),
+    pytest.param("DroneHoverSimpleEnv-v0", {}, 3000, 20, 20, id="simple"),
+    pytest.param("DroneHoverBulletFreeEnvWithDownwash-v0", {}, 3000, 20, 20, id="downwash"),
+    pytest.param("DroneHoverBulletFreeEnvWithConstWind-v0", {}, 3000, 20, 20, id="const-wind"),
+    pytest.param(FREE, dict(aggregate_phy_steps=1), 3000, 40, 60, id="agg1"),
+    pytest.param(FREE, dict(observation_noise=0, latency=0.02), 3000, 20, 20, id="noise-free-ring4"),
+    pytest.param("DroneHoverBulletFreeEnvWithGust-v0", {}, N1, 20, 20, id="gust-large"),
+]
+
+
+@pytest.mark.parametrize("env_id,kwargs,n,before,after", RESUME_CASES)
+def test_resume_from_checkpoint_is_bit_identical(gpu, tmp_path, env_id, kwargs, n, before, after):
     from cf2sim.vec_env import BatchedCrazyflieEnv
-    n = 3000
-    a_env = BatchedCrazyflieEnv(env_id, n, seed=8, env_id_offset=512, want_final_obs=True)
+    a_env = BatchedCrazyflieEnv(env_id, n, seed=8, env_id_offset=512, want_final_obs=True, **kwargs)
     a_env.reset()
     gen = torch.Generator(device="cuda")
     gen.manual_seed(2)
-    acts = [(torch.rand(n, 4, device="cuda", generator=gen) * 2 - 1).contiguous() for _ in range(40)]
-    for t in range(20):
+    acts = [(torch.rand(n, 4, device="cuda", generator=gen) * 2 - 1).contiguous() for _ in range(before + after)]
+    for t in range(before):
         a_env.step(acts[t])
     path = str(tmp_path / "batch.safetensors")
     a_env.save_checkpoint(path)
@@ -26,7 +44,7 @@ def test_resume_from_checkpoint_is_bit_identical(gpu, tmp_path, env_id):
     assert b_env.num_envs == n and b_env.want_final_obs
     np.testing.assert_array_equal(b_env.obs.cpu().numpy(), a_env.obs.cpu().numpy())
     dones = 0
-    for t in range(20, 40):
+    for t in range(before, before + after):
         oa, ra, da, ia = a_env.step(acts[t])
         ob, rb, db, ib = b_env.step(acts[t])
         np.testing.assert_array_equal(ob.cpu().numpy(), oa.cpu().numpy())
@@ -39,7 +57,7 @@ def test_resume_from_checkpoint_is_bit_identical(gpu, tmp_path, env_id):
     for x, y in zip(a_env.get_state(), b_env.get_state()):
         np.testing.assert_array_equal(x.cpu().numpy(), y.cpu().numpy())
     # a differently configured env refuses the checkpoint
-    other = BatchedCrazyflieEnv(env_id, n, seed=9, env_id_offset=512)
+    other = BatchedCrazyflieEnv(env_id, n, seed=9, env_id_offset=512, **kwargs)
     with pytest.raises(ValueError):
         other.load_checkpoint(path)
     for e in (a_env, b_env, other):
