@@ -6,8 +6,9 @@ phoenix_drone_simulation, the package of Hu-Hanyang/disturbance-CrazyFile-simula
 * ``cf2sim.physics``: the reference's physics plugin classes (``PybulletPhysicsWithAdversary``, ...,
   ``HipBatchedPhysics``) over the HIP physics kernel, for ``getattr(module, physics)`` lookups.
 * ``solve_value_tables(cfg)``: the HJ-adversary envs' value tables, solved on the GPU (hj_solve.py).
-* ``Population`` / ``collect_population`` / ``PopulationPPOUpdater``: P independent learners on one env
-  batch, collected and updated with launch counts that do not depend on P (population.py).
+* ``Population`` / ``collect_population`` / ``PopulationPPOUpdater`` / ``PopulationNaturalGradientUpdater``:
+  P independent learners on one env batch, collected and updated (PPO, TRPO, NPG) with launch counts
+  that do not depend on P (population.py).
 """
 from .config import (ENV_SPECS, OUT_OF_SCOPE_IDS, REFERENCE_IDS, CF2Config, build_config,  # noqa: F401
                      spec_for_id)
@@ -15,10 +16,12 @@ from .config import (ENV_SPECS, OUT_OF_SCOPE_IDS, REFERENCE_IDS, CF2Config, buil
 __all__ = ["ENV_SPECS", "REFERENCE_IDS", "OUT_OF_SCOPE_IDS", "CF2Config", "build_config", "spec_for_id",
            "BatchedCrazyflieEnv", "make", "registry",
            "HJModel", "default_target", "time_step", "solve_value_table", "solve_value_tables", "save_value_tables",
-           "Population", "PopulationRollout", "collect_population", "PopulationPPOUpdater"]
+           "Population", "PopulationRollout", "collect_population", "PopulationPPOUpdater",
+           "PopulationNaturalGradientUpdater"]
 
 _HJ_SOLVE = ("HJModel", "default_target", "time_step", "solve_value_table", "solve_value_tables", "save_value_tables")
-_POPULATION = ("Population", "PopulationRollout", "collect_population", "PopulationPPOUpdater")
+_POPULATION = ("Population", "PopulationRollout", "collect_population", "PopulationPPOUpdater",
+               "PopulationNaturalGradientUpdater")
 
 
 def __getattr__(name):   # lazy: importing the package must not require torch / a GPU

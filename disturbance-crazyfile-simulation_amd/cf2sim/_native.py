@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "cf2_set_level_distribution",
     "cf2_policy_forward_pop",
     "cf2_ppo_pop_scratch_bytes", "cf2_ppo_policy_grad_pop", "cf2_ppo_value_grad_pop", "cf2_adam_step_pop",
+    "cf2_ppo_fisher_vec_pop", "cf2_ng_cg_init_pop", "cf2_ng_cg_step_pop", "cf2_ng_direction_pop", "cf2_ng_line_search_pop",
 )
 # declared too, but returning uint32_t: the header scan of tests/test_abi.py lists the int, size_t and
 # const char* entry points, which EXPORTED_SYMBOLS must equal (tests/test_population_cpu.py checks these)
@@ -150,6 +151,11 @@ def load() -> ctypes.CDLL:
                                             vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp]
     lib.cf2_ppo_value_grad_pop.argtypes = [u32, vp, sz, u32, vp, sz, vp, sz, u32, vp, sz, u32, vp, sz, vp, vp, vp, vp, vp]
     lib.cf2_adam_step_pop.argtypes = [u32, vp, vp, vp, vp, sz, u32, u32, vp, vp] + [ctypes.c_float] * 3 + [vp] * 6
+    lib.cf2_ppo_fisher_vec_pop.argtypes = [u32, vp, sz, u32, vp, sz, u32, vp, sz, u32, vp, sz, vp, sz, vp, vp, vp, vp]
+    lib.cf2_ng_cg_init_pop.argtypes = [u32] + [vp] * 5 + [sz, u32, u32, vp, vp, vp]
+    lib.cf2_ng_cg_step_pop.argtypes = [u32] + [vp] * 4 + [sz, u32, u32, vp, vp, vp, vp]
+    lib.cf2_ng_direction_pop.argtypes = [u32] + [vp] * 6 + [sz, u32, u32, vp, vp, vp, vp, vp]
+    lib.cf2_ng_line_search_pop.argtypes = [u32] + [vp] * 3 + [sz] + [u32] * 4 + [ctypes.c_float, vp, vp, vp, sz, vp, vp, vp]
     lib.cf2_ppo_fisher_vec.argtypes =[vp, u32, vp, u32, vp, u32] + [vp] * 6
     lib.cf2_ng_cg_init.argtypes = [vp] * 5 + [u32, u32, vp, vp, vp]
     lib.cf2_ng_cg_step.argtypes = [vp] * 4 + [u32, u32, ctypes.c_float, vp, vp, vp]

@@ -19,12 +19,17 @@ is keyed by the global env id, so one context of P * n envs is bit for bit P con
   length does not depend on P (cf2_ppo_policy_grad_pop, cf2_ppo_value_grad_pop, cf2_adam_step_pop),
   reading the member-major storage in place; per-member learning rates, clip ratios, KL targets and
   gradient-norm limits, each member stopping at its own iteration.
+* ``PopulationNaturalGradientUpdater``: the resident TRPO / NPG update of all members likewise
+  (cf2_ppo_fisher_vec_pop and the four cf2_ng_*_pop solver launches); per-member KL targets, CG
+  dampings, value learning rates and gradient-norm limits, each member's conjugate gradients and
+  line search stopping on their own.
 
 Every member's whole training run is bit-identical to the run it has alone on
 ``BatchedCrazyflieEnv(id, n, seed=s, env_id_offset=m * n)`` with ``FusedActorCritic(ac_m, seed_m)``
-and ``ResidentPPOUpdater(ac_m, ...)`` (tests/test_population_gpu.py,
-tests/test_population_update_gpu.py).  Not covered: per-member weights inside the fused collect
-kernels, TRPO / NPG updates of a population, ``group=`` and formations.
+and ``ResidentPPOUpdater(ac_m, ...)`` or ``NaturalGradientUpdater(ac_m, ...)``
+(tests/test_population_gpu.py, tests/test_population_update_gpu.py,
+tests/test_population_natgrad_gpu.py).  Not covered: per-member weights inside the fused collect
+kernels, ``group=`` and formations.
 """
 from __future__ import annotations
 
@@ -290,12 +295,122 @@ def member_stride(tensors, name: str) -> int:
     es, base = t0.element_size(), t0.data_ptr()
     step = tensors[1].data_ptr() - base
     if step % es or step < t0.numel() * es or any(t.data_ptr() != base + k * step for k, t in enumerate(tensors)):
-        raise ValueError(f"the members' {name} are not equally spaced slices of one buffer: a PopulationPPOUpdater "
+        raise ValueError(f"the members' {name} are not equally spaced slices of one buffer: a population updater "
                          "updates from the member-major storage of collect_population")
     return step // es
 
 
-class PopulationPPOUpdater:
+class _PopulationUpdaterShared:
+    """What the population updaters share (``PopulationPPOUpdater``, ``PopulationNaturalGradientUpdater``):
+    the per-member optimiser states ``self.opt`` and their ``state_dict``, the view of a
+    ``PopulationRollout`` as one base tensor and one member stride per row buffer, the per-member
+    plumbing at both ends of an update and the value phase.  A class using it has ``pop``,
+    ``generators``, ``count``, ``pi_slice``, ``v_slice``, ``flat``, ``grad``, ``opt``, ``betas``, ``eps``,
+    ``v_lr_dev`` (``pi_lr_dev`` where it steps the policy with Adam), ``target_kl_dev``,
+    ``max_grad_norm_dev``, ``summary_mb``, ``train_v_iterations`` and ``num_mini_batches``."""
+
+    @staticmethod
+    def _check_generators(generators, P: int):
+        if generators is not None:
+            generators = list(generators)
+            if len(generators) != P or any(not isinstance(g, torch.Generator) for g in generators):
+                raise ValueError(f"generators must be None or {P} torch.Generators, one per member")
+        return generators
+
+    def state_dict(self) -> list:
+        return [{w: {"exp_avg": s["exp_avg"][k].clone(), "exp_avg_sq": s["exp_avg_sq"][k].clone(),
+                     "step": s["step"][k:k + 1].clone()} for w, s in self.opt.items()} for k in range(len(self.pop))]
+
+    def load_state_dict(self, sd) -> None:
+        sd = list(sd)
+        if len(sd) != len(self.pop):
+            raise ValueError(f"expected {len(self.pop)} entries, one per member, got {len(sd)}")
+        for k, entry in enumerate(sd):
+            for w, s in self.opt.items():
+                s["exp_avg"][k].copy_(entry[w]["exp_avg"])
+                s["exp_avg_sq"][k].copy_(entry[w]["exp_avg_sq"])
+                s["step"][k:k + 1].copy_(entry[w]["step"])
+
+    def _adam(self, which: str, kl_summary=None, ctrl=None) -> None:
+        from . import _native
+        s, (b0, b1) = self.opt[which], self.pi_slice if which == "pi" else self.v_slice
+        p = _native.ptr
+        _native.check(self.pop.lib.cf2_adam_step_pop(
+            len(self.pop), p(self.flat), p(self.grad), p(s["exp_avg"]), p(s["exp_avg_sq"]), self.count, b0, b1 - b0,
+            p(s["step"]), p(self.pi_lr_dev if which == "pi" else self.v_lr_dev), self.betas[0], self.betas[1], self.eps,
+            p(self.max_grad_norm_dev), p(s["norm"]), p(kl_summary), p(self.target_kl_dev), p(ctrl),
+            torch.cuda.current_stream(self.flat.device).cuda_stream), "cf2_adam_step_pop")
+
+    def _member_views(self, rollout: "PopulationRollout"):
+        """(members, rows, base, stride): the rollout's row buffers as member 0's tensor and the member
+        stride in elements, per name; ValueError where they are not the member-major storage."""
+        P, d, dev = len(self.pop), self.pop.obs_dim, self.flat.device
+        ms = list(rollout.members)
+        if len(ms) != P:
+            raise ValueError(f"the rollout has {len(ms)} members, the population {P}")
+        obs0 = ms[0].obs
+        if obs0.dim() != 3 or obs0.shape[-1] != d or obs0.device != dev or obs0.dtype != torch.float32:
+            raise ValueError(f"a member's obs must be float32 [T, n, {d}] on {dev}, got {tuple(obs0.shape)} on {obs0.device}")
+        rows = obs0.shape[0] * obs0.shape[1]
+        if rows == 0 or rows >= 2 ** 31:
+            raise ValueError(f"a rollout of {rows} rows per member cannot be updated from in one call")
+        want = {"obs": (*obs0.shape[:2], d), "act": (*obs0.shape[:2], 4), "logp": tuple(obs0.shape[:2]),
+                "adv": tuple(obs0.shape[:2]), "ret": tuple(obs0.shape[:2])}
+        base, stride = {}, {}
+        for name, shape in want.items():
+            ts = [getattr(r, name) for r in ms]
+            if tuple(ts[0].shape) != shape or ts[0].dtype != torch.float32 or ts[0].device != dev:
+                raise ValueError(f"a member's {name} must be float32 {shape} on {dev}")
+            base[name], stride[name] = ts[0], member_stride(ts, name)
+        if stride["obs"] % 2 or stride["act"] % 4 or base["obs"].data_ptr() % 8 or base["act"].data_ptr() % 16:
+            raise ValueError("the members' obs must be 8-byte and their act 16-byte aligned")
+        return ms, rows, base, stride
+
+    def _begin(self, ms, rows: int, idx, mom, scratch, stream) -> None:
+        """Every value pass's permutations, the members' advantage moments and packed flat blocks."""
+        from . import _native
+        P, dev = len(self.pop), self.flat.device
+        # Every value pass's permutations, member k's drawn with generators[k] in pass order exactly as
+        # PPOUpdater.value_minibatches draws them, but all before the first launch: torch.randperm on the
+        # GPU waits for the work already enqueued (measured at 32 768 and 131 072 rows, not at 1 048 576),
+        # which between the passes would stall the host once per member and pass.
+        for v in range(self.train_v_iterations):
+            for k in range(P):
+                g = self.generators[k] if self.generators is not None else None
+                idx[v, k].copy_(torch.randperm(rows, generator=g, device=g.device if g is not None else dev))
+        for k in range(P):        # per-member plumbing, once per update
+            _native.check(self.pop.lib.cf2_column_moments(ms[k].adv.data_ptr(), rows, 1, mom[k].data_ptr(),
+                                                          scratch.data_ptr(), stream), "cf2_column_moments")
+            self.flat[k].copy_(pack_policy_weights(self.pop.acs[k]))
+
+    def _value_call(self, rows: int, base, stride, scratch, stream):
+        """``val(summary, grad=None, idx_ptr=None, m=rows)``: cf2_ppo_value_grad_pop on the rollout."""
+        from . import _native
+        pop, p = self.pop, _native.ptr
+
+        def val(summ, grad=None, idx_ptr=None, m=rows):
+            _native.check(pop.lib.cf2_ppo_value_grad_pop(
+                len(pop), p(self.flat), self.count, pop.obs_dim, p(base["obs"]), stride["obs"], p(base["ret"]),
+                stride["ret"], rows, idx_ptr, rows, m, None, 0, p(grad), p(summ), p(scratch), None, stream),
+                "cf2_ppo_value_grad_pop")
+        return val
+
+    def _value_phase(self, val, idx, rows: int) -> None:
+        nb = min(self.num_mini_batches, rows)
+        for v in range(self.train_v_iterations):
+            for j in range(nb):           # the members' j-th pieces of pass v's permutations
+                lo, hi = (j * rows) // nb, ((j + 1) * rows) // nb
+                val(self.summary_mb, grad=self.grad, idx_ptr=idx[v].data_ptr() + 4 * lo, m=hi - lo)
+                self._adam("v")
+
+    def _end(self) -> None:
+        from .rollout import unpack_policy_weights
+        for k in range(len(self.pop)):
+            unpack_policy_weights(self.pop.acs[k], self.flat[k])
+            self.pop.member(k).sync_from_flat(self.flat[k])
+
+
+class PopulationPPOUpdater(_PopulationUpdaterShared):
     """``ResidentPPOUpdater`` for all members of a ``Population`` at once: the launch sequence of one
     resident update, every launch serving the P members (cf2_ppo_policy_grad_pop,
     cf2_ppo_value_grad_pop, cf2_adam_step_pop), so an update is a number of launches that does not
@@ -333,10 +448,7 @@ class PopulationPPOUpdater:
         if any(not (lr >= 0.0 and math.isfinite(lr)) for lr in self.pi_lr + self.v_lr) \
                 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or not eps >= 0.0:
             raise ValueError(f"invalid Adam hyper-parameters pi_lr={pi_lr} v_lr={v_lr} betas={betas} eps={eps}")
-        if generators is not None:
-            generators = list(generators)
-            if len(generators) != P or any(not isinstance(g, torch.Generator) for g in generators):
-                raise ValueError(f"generators must be None or {P} torch.Generators, one per member")
+        generators = self._check_generators(generators, P)
         dev = torch.device(pop.device)
         if dev.type != "cuda":
             raise ValueError("PopulationPPOUpdater needs the population on the GPU")
@@ -358,20 +470,6 @@ class PopulationPPOUpdater:
         self.ctrl = z(P, 4, dt=torch.int32)
         self.summary0, self.summary, self.summary_v, self.summary_mb = (z(P, 8, dt=torch.float64) for _ in range(4))
         self._bufs, self._pending = None, None
-
-    def state_dict(self) -> list:
-        return [{w: {"exp_avg": s["exp_avg"][k].clone(), "exp_avg_sq": s["exp_avg_sq"][k].clone(),
-                     "step": s["step"][k:k + 1].clone()} for w, s in self.opt.items()} for k in range(len(self.pop))]
-
-    def load_state_dict(self, sd) -> None:
-        sd = list(sd)
-        if len(sd) != len(self.pop):
-            raise ValueError(f"expected {len(self.pop)} entries, one per member, got {len(sd)}")
-        for k, entry in enumerate(sd):
-            for w, s in self.opt.items():
-                s["exp_avg"][k].copy_(entry[w]["exp_avg"])
-                s["exp_avg_sq"][k].copy_(entry[w]["exp_avg_sq"])
-                s["step"][k:k + 1].copy_(entry[w]["step"])
 
     def result(self) -> list | None:
         """The last update's results, one dict of ``ResidentPPOUpdater.KEYS`` per member (one device
@@ -395,57 +493,17 @@ class PopulationPPOUpdater:
                           "moments": torch.empty(P, 2, dtype=torch.float64, device=dev)}
         return self._bufs
 
-    def _adam(self, which: str, kl_summary=None, ctrl=None) -> None:
-        from . import _native
-        s, (b0, b1) = self.opt[which], self.pi_slice if which == "pi" else self.v_slice
-        p = _native.ptr
-        _native.check(self.pop.lib.cf2_adam_step_pop(
-            len(self.pop), p(self.flat), p(self.grad), p(s["exp_avg"]), p(s["exp_avg_sq"]), self.count, b0, b1 - b0,
-            p(s["step"]), p(self.pi_lr_dev if which == "pi" else self.v_lr_dev), self.betas[0], self.betas[1], self.eps,
-            p(self.max_grad_norm_dev), p(s["norm"]), p(kl_summary), p(self.target_kl_dev), p(ctrl),
-            torch.cuda.current_stream(self.flat.device).cuda_stream), "cf2_adam_step_pop")
-
     @torch.no_grad()
     def update(self, rollout: PopulationRollout, read: bool = True):
         from . import _native
-        from .rollout import unpack_policy_weights
         pop, lib, p = self.pop, self.pop.lib, _native.ptr
         P, d, dev = len(pop), pop.obs_dim, self.flat.device
-        ms = list(rollout.members)
-        if len(ms) != P:
-            raise ValueError(f"the rollout has {len(ms)} members, the population {P}")
-        obs0 = ms[0].obs
-        if obs0.dim() != 3 or obs0.shape[-1] != d or obs0.device != dev or obs0.dtype != torch.float32:
-            raise ValueError(f"a member's obs must be float32 [T, n, {d}] on {dev}, got {tuple(obs0.shape)} on {obs0.device}")
-        rows = obs0.shape[0] * obs0.shape[1]
-        if rows == 0 or rows >= 2 ** 31:
-            raise ValueError(f"a rollout of {rows} rows per member cannot be updated from in one call")
-        want = {"obs": (*obs0.shape[:2], d), "act": (*obs0.shape[:2], 4), "logp": tuple(obs0.shape[:2]),
-                "adv": tuple(obs0.shape[:2]), "ret": tuple(obs0.shape[:2])}
-        base, stride = {}, {}
-        for name, shape in want.items():
-            ts = [getattr(r, name) for r in ms]
-            if tuple(ts[0].shape) != shape or ts[0].dtype != torch.float32 or ts[0].device != dev:
-                raise ValueError(f"a member's {name} must be float32 {shape} on {dev}")
-            base[name], stride[name] = ts[0], member_stride(ts, name)
-        if stride["obs"] % 2 or stride["act"] % 4 or base["obs"].data_ptr() % 8 or base["act"].data_ptr() % 16:
-            raise ValueError("the members' obs must be 8-byte and their act 16-byte aligned")
+        ms, rows, base, stride = self._member_views(rollout)
         B = self._buffers(rows, dev)
         scratch, idx, mu_old, mom = B["scratch"], B["idx"], B["mu_old"], B["moments"]
         flat, grad, ctrl, summary0, summary = self.flat, self.grad, self.ctrl, self.summary0, self.summary
         stream = torch.cuda.current_stream(dev).cuda_stream
-        # Every value pass's permutations, member k's drawn with generators[k] in pass order exactly as
-        # PPOUpdater.value_minibatches draws them, but all before the first launch: torch.randperm on the
-        # GPU waits for the work already enqueued (measured at 32 768 and 131 072 rows, not at 1 048 576),
-        # which between the passes would stall the host once per member and pass.
-        for v in range(self.train_v_iterations):
-            for k in range(P):
-                g = self.generators[k] if self.generators is not None else None
-                idx[v, k].copy_(torch.randperm(rows, generator=g, device=g.device if g is not None else dev))
-        for k in range(P):        # per-member plumbing, once per update
-            _native.check(lib.cf2_column_moments(ms[k].adv.data_ptr(), rows, 1, mom[k].data_ptr(), scratch.data_ptr(),
-                                                 stream), "cf2_column_moments")
-            flat[k].copy_(pack_policy_weights(pop.acs[k]))
+        self._begin(ms, rows, idx, mom, scratch, stream)
 
         def pol(summ, grad=None, mu_old=None, mu_out=None, gate=None):
             _native.check(lib.cf2_ppo_policy_grad_pop(
@@ -454,11 +512,7 @@ class PopulationPPOUpdater:
                 4 * rows, p(mu_out), 4 * rows, None, 0, p(grad), p(summ), p(scratch), p(gate), stream),
                 "cf2_ppo_policy_grad_pop")
 
-        def val(summ, grad=None, idx_ptr=None, m=rows):
-            _native.check(lib.cf2_ppo_value_grad_pop(
-                P, p(flat), self.count, d, p(base["obs"]), stride["obs"], p(base["ret"]), stride["ret"], rows, idx_ptr,
-                rows, m, None, 0, p(grad), p(summ), p(scratch), None, stream), "cf2_ppo_value_grad_pop")
-
+        val = self._value_call(rows, base, stride, scratch, stream)
         ctrl.zero_()
         summary.zero_()                   # KL and ClipFrac of an update without a policy step
         val(self.summary_v)
@@ -470,19 +524,171 @@ class PopulationPPOUpdater:
                 pol(summary, grad=grad, mu_old=mu_old, gate=ctrl)
                 self._adam("pi", kl_summary=summary, ctrl=ctrl)
             pol(summary, mu_old=mu_old, gate=ctrl)
-        nb = min(self.num_mini_batches, rows)
-        for v in range(self.train_v_iterations):
-            for j in range(nb):           # the members' j-th pieces of pass v's permutations
-                lo, hi = (j * rows) // nb, ((j + 1) * rows) // nb
-                val(self.summary_mb, grad=grad, idx_ptr=idx[v].data_ptr() + 4 * lo, m=hi - lo)
-                self._adam("v")
-        for k in range(P):
-            unpack_policy_weights(pop.acs[k], flat[k])
-            pop.member(k).sync_from_flat(flat[k])
+        self._value_phase(val, idx, rows)
+        self._end()
         self._pending = torch.cat([summary0[:, 1:2], self.summary_v[:, 1:2], summary[:, 4:5], summary[:, 3:4],
                                    ctrl[:, 1:2].double(), self.opt["pi"]["norm"][:, None]], dim=1)
         return self.result() if read else None
 
 
-__all__ = ["Population", "PopulationMember", "PopulationPPOUpdater", "PopulationRollout", "collect_population",
-           "member_major", "member_stride", "per_member", "rows_per_member"]
+class PopulationNaturalGradientUpdater(_PopulationUpdaterShared):
+    """``NaturalGradientUpdater(device=True)`` (TRPO, NPG) for all members of a ``Population`` at once:
+    the launch sequence of one resident update -- the starting gradient G0, conjugate gradients with
+    the Fisher-vector products, the step, TRPO's line search or NPG's evaluation, then the value
+    phase -- every launch serving the P members (cf2_ppo_policy_grad_pop, cf2_ppo_fisher_vec_pop,
+    cf2_ng_cg_init_pop, cf2_ng_cg_step_pop, cf2_ng_direction_pop, cf2_ng_line_search_pop,
+    cf2_ppo_value_grad_pop, cf2_adam_step_pop), so an update is a number of launches that does not
+    depend on P.  Member k's update is bit for bit the one
+    ``NaturalGradientUpdater(pop.acs[k], v_lr[k], target_kl[k], ..., fused=pop.member(k),
+    generator=generators[k])`` makes on ``rollout.members[k]`` (tests/test_population_natgrad_gpu.py).
+
+    ``v_lr``, ``target_kl``, ``cg_damping`` and ``max_grad_norm`` are each a scalar or a sequence of P
+    values, held in device arrays; ``algorithm``, the iteration counts, ``fvp_stride``, the line
+    search's length and decay, the number of mini-batches, the betas and eps are shared.  Every
+    member has its own solver state, control block and summaries: a member whose conjugate
+    gradients have converged, or whose line search has accepted or given up, is skipped by the later
+    launches while the others go on.  ``generators``: as ``PopulationPPOUpdater``'s.
+
+    The row buffers are the rollout's member-major storage, read in place; the Fisher-vector
+    products read every ``fvp_stride``-th row through one index list that all members share.
+    ``update(rollout, read=False)`` never waits for the GPU; ``result()`` reads the P x 10 results in
+    one transfer, one dict of ``NaturalGradientUpdater.KEYS`` per member.  ``state_dict()`` is a list
+    of P entries, entry k interchangeable with ``NaturalGradientUpdater.state_dict()`` of the
+    stand-alone learner.  The per-member torch plumbing is ``PopulationPPOUpdater``'s."""
+
+    def __init__(self, pop: Population, v_lr, target_kl, algorithm: str = "trpo", cg_iters: int = 10, cg_damping=0.1,
+                 fvp_stride: int = 4, line_search_steps: int = 25, line_search_decay: float = 0.8,
+                 train_v_iterations: int = 5, num_mini_batches: int = 16, betas=(0.9, 0.999), eps: float = 1e-8,
+                 max_grad_norm=None, generators=None):
+        from .ppo import NG_STATE_DOUBLES, flat_slice
+        P = len(pop)
+        if algorithm not in ("trpo", "npg"):
+            raise ValueError(f"algorithm must be 'trpo' or 'npg', got {algorithm!r}")
+        self.v_lr, self.target_kl = per_member(v_lr, P, "v_lr"), per_member(target_kl, P, "target_kl")
+        self.cg_damping = per_member(cg_damping, P, "cg_damping")
+        self.max_grad_norm = per_member(max_grad_norm, P, "max_grad_norm", none=0.0)
+        if num_mini_batches < 1 or fvp_stride < 1 or cg_iters < 0 or line_search_steps < 1:
+            raise ValueError("num_mini_batches, fvp_stride and line_search_steps must be at least 1, cg_iters at least 0")
+        if any(not (t >= 0.0 and math.isfinite(t)) for t in self.target_kl + self.cg_damping) \
+                or not 0.0 < line_search_decay <= 1.0:
+            raise ValueError("target_kl and cg_damping must not be negative (and finite, for every member), "
+                             "line_search_decay must lie in (0, 1]")
+        if any(not (lr >= 0.0 and math.isfinite(lr)) for lr in self.v_lr) \
+                or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or not eps >= 0.0:
+            raise ValueError(f"invalid Adam hyper-parameters v_lr={v_lr} betas={betas} eps={eps}")
+        generators = self._check_generators(generators, P)
+        dev = torch.device(pop.device)
+        if dev.type != "cuda":
+            raise ValueError("PopulationNaturalGradientUpdater needs the population on the GPU")
+        self.pop, self.generators, self.algorithm = pop, generators, algorithm
+        self.cg_iters, self.fvp_stride = int(cg_iters), int(fvp_stride)
+        self.line_search_steps, self.line_search_decay = int(line_search_steps), float(line_search_decay)
+        self.train_v_iterations, self.num_mini_batches = int(train_v_iterations), int(num_mini_batches)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        ac = pop.acs[0]
+        self.count = flat_slice(ac, "v")[1] + 2 * pop.obs_dim
+        self.pi_slice, self.v_slice = flat_slice(ac, "pi"), flat_slice(ac, "v")
+        f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)
+        self.v_lr_dev, self.target_kl_dev, self.damping_dev = f32(self.v_lr), f32(self.target_kl), f32(self.cg_damping)
+        self.max_grad_norm_dev = f32(self.max_grad_norm)
+        self.clip_dev = f32([float("inf")] * P)       # the unclipped surrogate -mean(ratio A)
+        z = lambda *shape, dt=torch.float32: torch.zeros(*shape, dtype=dt, device=dev)
+        self.flat, self.grad = z(P, self.count), z(P, self.count)
+        self.work = {k: z(P, self.count) for k in ("b", "x", "r", "p", "z", "step", "old")}
+        self.opt = {"v": {"exp_avg": z(P, self.count), "exp_avg_sq": z(P, self.count), "step": z(P, dt=torch.int32),
+                          "norm": z(P, dt=torch.float64)}}
+        self.ctrl = z(P, 4, dt=torch.int32)
+        self.ng_state = z(P, NG_STATE_DOUBLES, dt=torch.float64)
+        self.summary0, self.summary, self.summary_v, self.summary_mb, self.summary_f = (
+            z(P, 8, dt=torch.float64) for _ in range(5))
+        self._bufs, self._pending = None, None
+
+    def result(self) -> list | None:
+        """The last update's results, one dict of ``NaturalGradientUpdater.KEYS`` per member (one device
+        read); None before the first update."""
+        from .ppo import NaturalGradientUpdater
+        if self._pending is None:
+            return None
+        out = [dict(zip(NaturalGradientUpdater.KEYS, row)) for row in self._pending.tolist()]
+        for o in out:
+            o["AcceptanceStep"] = int(o["AcceptanceStep"])
+        return out
+
+    def _buffers(self, rows: int, dev):
+        key = (rows, self.fvp_stride, str(dev))
+        if self._bufs is None or self._bufs["key"] != key:
+            lib, P, d = self.pop.lib, len(self.pop), self.pop.obs_dim
+            nbytes = max(lib.cf2_ppo_pop_scratch_bytes(P, rows, d), lib.cf2_column_moments_scratch_bytes(rows, 1))
+            self._bufs = {"key": key, "scratch": torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev),
+                          "idx": torch.empty(self.train_v_iterations, P, rows, dtype=torch.int32, device=dev),
+                          "fvp_idx": torch.arange(0, rows, self.fvp_stride, dtype=torch.int32, device=dev),
+                          "mu_old": torch.empty(P, rows, 4, device=dev),
+                          "moments": torch.empty(P, 2, dtype=torch.float64, device=dev)}
+        return self._bufs
+
+    @torch.no_grad()
+    def update(self, rollout: PopulationRollout, read: bool = True):
+        from . import _native
+        from .ppo import (NG_ACCEPT_STEP, NG_ALPHA, NG_BDOTB, NG_EXPECTED, NG_KL_AFTER, NG_RESIDUAL, NG_STEP_FRAC,
+                          NG_XHX)
+        pop, lib, p = self.pop, self.pop.lib, _native.ptr
+        P, d, dev, count = len(pop), pop.obs_dim, self.flat.device, self.count
+        ms, rows, base, stride = self._member_views(rollout)
+        B = self._buffers(rows, dev)
+        scratch, idx, fidx, mu_old, mom = B["scratch"], B["idx"], B["fvp_idx"], B["mu_old"], B["moments"]
+        flat, grad, ctrl, st, W = self.flat, self.grad, self.ctrl, self.ng_state, self.work
+        summary0, summary = self.summary0, self.summary
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._begin(ms, rows, idx, mom, scratch, stream)
+
+        def pol(summ, grad=None, mu_old=None, mu_out=None, gate=None):
+            _native.check(lib.cf2_ppo_policy_grad_pop(
+                P, p(flat), count, d, p(base["obs"]), stride["obs"], p(base["act"]), stride["act"], p(base["logp"]),
+                stride["logp"], p(base["adv"]), stride["adv"], rows, None, 0, rows, p(mom), p(self.clip_dev), p(mu_old),
+                4 * rows, p(mu_out), 4 * rows, None, 0, p(grad), p(summ), p(scratch), p(gate), stream),
+                "cf2_ppo_policy_grad_pop")
+
+        def fvp(vec):             # z = F vec on every fvp_stride-th row: one list for all members
+            _native.check(lib.cf2_ppo_fisher_vec_pop(
+                P, p(flat), count, d, p(base["obs"]), stride["obs"], rows, p(fidx), 0, fidx.numel(), p(vec), count,
+                p(W["z"]), count, p(self.summary_f), p(scratch), None, stream), "cf2_ppo_fisher_vec_pop")
+
+        val = self._value_call(rows, base, stride, scratch, stream)
+        p0, p1 = self.pi_slice
+        ctrl.zero_()
+        val(self.summary_v)
+        pol(summary0, mu_out=mu_old, grad=grad)
+        _native.check(lib.cf2_ng_cg_init_pop(P, p(grad), p(W["b"]), p(W["x"]), p(W["r"]), p(W["p"]), count, p0, p1 - p0,
+                                             p(st), None, stream), "cf2_ng_cg_init_pop")
+        for _ in range(self.cg_iters):
+            fvp(W["p"])
+            _native.check(lib.cf2_ng_cg_step_pop(P, p(W["z"]), p(W["x"]), p(W["r"]), p(W["p"]), count, p0, p1 - p0,
+                                                 p(self.damping_dev), p(st), None, stream), "cf2_ng_cg_step_pop")
+        fvp(W["x"])
+        _native.check(lib.cf2_ng_direction_pop(P, p(W["z"]), p(W["x"]), p(W["b"]), p(W["step"]), p(flat), p(W["old"]), count,
+                                               p0, p1 - p0, p(self.damping_dev), p(self.target_kl_dev), p(st), None,
+                                               stream), "cf2_ng_direction_pop")
+        if self.algorithm == "trpo":
+            for j in range(self.line_search_steps):
+                pol(summary, mu_old=mu_old, gate=ctrl)
+                _native.check(lib.cf2_ng_line_search_pop(
+                    P, p(flat), p(W["old"]), p(W["step"]), count, p0, p1 - p0, j, self.line_search_steps,
+                    self.line_search_decay, p(self.target_kl_dev), p(summary), summary0.data_ptr() + 8, 8, p(st), p(ctrl),
+                    stream), "cf2_ng_line_search_pop")
+            after = [st[:, NG_KL_AFTER:NG_KL_AFTER + 1], st[:, NG_ACCEPT_STEP:NG_ACCEPT_STEP + 1],
+                     st[:, NG_STEP_FRAC:NG_STEP_FRAC + 1]]
+        else:
+            pol(summary, mu_old=mu_old)
+            one = torch.ones(P, 1, dtype=torch.float64, device=dev)
+            after = [summary[:, 4:5], one, one]
+        self._value_phase(val, idx, rows)
+        self._end()
+        self._pending = torch.cat([summary0[:, 1:2], self.summary_v[:, 1:2], after[0], after[1], after[2],
+                                   st[:, NG_XHX:NG_XHX + 1], st[:, NG_ALPHA:NG_ALPHA + 1],
+                                   st[:, NG_EXPECTED:NG_EXPECTED + 1], st[:, NG_RESIDUAL:NG_RESIDUAL + 1].sqrt(),
+                                   st[:, NG_BDOTB:NG_BDOTB + 1].sqrt()], dim=1)
+        return self.result() if read else None
+
+
+__all__ = ["Population", "PopulationMember", "PopulationNaturalGradientUpdater", "PopulationPPOUpdater",
+           "PopulationRollout", "collect_population", "member_major", "member_stride", "per_member", "rows_per_member"]

@@ -13,6 +13,9 @@
 // arithmetic.  Being the only workgroup a kernel can read and write the scalars of ng_state and the
 // stop flag without a race: every thread reads them, a barrier follows, and only then thread 0 writes.
 //
+// The cf2_ng_*_pop entry points launch the same bodies with one workgroup per member of a population
+// (the <true> instances; NgCgPopArgs below).
+//
 // The rules (the reference's algs/npg and algs/trpo) are spelled out at the entry points in
 // include/cf2sim.h; ng_state's layout is CF2_NG_* there.
 #include <hip/hip_runtime.h>
@@ -62,7 +65,39 @@ struct NgCgArgs {
     float damping;
 };
 
-__global__ void __launch_bounds__(NG_BLOCK) ng_cg_init_kernel(const NgCgArgs a) {
+// P members in one launch (cf2_ng_*_pop; the <true> instances): workgroup k is member k's kernel on
+// the blocks k `stride` floats further on, with ng_state + 16 k, the control block ctrl + 4 k and the
+// member's own damping[k] and target_kl[k].  It is the only writer of member k's words (state, stop
+// flag and weights among them) and never looks at another member's, so the header comment's argument
+// holds per member.  `base` holds member 0's pointers; its damping and target_kl are unused.
+struct NgCgPopArgs {
+    NgCgArgs base;
+    size_t stride;               // floats between the members' blocks
+    const float* damping;        // [P]; nullptr (cg_init): not read
+};
+
+// what a kernel instance is launched with and the arguments its body sees; the stand-alone instance
+// reads its own kernel argument, as before (cf2sim_ppo.hip, PpoKernelArgs, has the reason)
+template <bool POP> struct NgCgKernelArgs { using type = NgCgArgs; };
+template <> struct NgCgKernelArgs<true> { using type = NgCgPopArgs; };
+__device__ __forceinline__ const NgCgArgs& ng_args_of(const NgCgArgs& a) { return a; }
+__device__ __forceinline__ NgCgArgs ng_args_of(const NgCgPopArgs& p) {
+    const uint32_t k = blockIdx.x;
+    NgCgArgs a = p.base;
+    a.in += k * p.stride;
+    if (a.b) a.b += k * p.stride;
+    a.x += k * p.stride;
+    a.r += k * p.stride;
+    a.p += k * p.stride;
+    a.st += (size_t)CF2_NG_STATE_DOUBLES * k;
+    if (a.gate) a.gate += 4u * (size_t)k;
+    if (p.damping) a.damping = p.damping[k];
+    return a;
+}
+
+template <bool POP = false>
+__global__ void __launch_bounds__(NG_BLOCK) ng_cg_init_kernel(const typename NgCgKernelArgs<POP>::type ka) {
+    const NgCgArgs a = ng_args_of(ka);
     __shared__ double wsum[NG_WAVES];
     const uint32_t tid = threadIdx.x;
     if (a.gate && a.gate[0] != 0u) return;
@@ -80,7 +115,9 @@ __global__ void __launch_bounds__(NG_BLOCK) ng_cg_init_kernel(const NgCgArgs a) 
     if (k < CF2_NG_STATE_DOUBLES) a.st[k] = (k == CF2_NG_RDOTR || k == CF2_NG_BDOTB || k == CF2_NG_RESIDUAL) ? bb : 0.0;
 }
 
-__global__ void __launch_bounds__(NG_BLOCK) ng_cg_step_kernel(const NgCgArgs a) {
+template <bool POP = false>
+__global__ void __launch_bounds__(NG_BLOCK) ng_cg_step_kernel(const typename NgCgKernelArgs<POP>::type ka) {
+    const NgCgArgs a = ng_args_of(ka);
     __shared__ double wsum[NG_WAVES];
     const uint32_t tid = threadIdx.x;
     const bool stopped = a.gate && a.gate[0] != 0u;
@@ -133,7 +170,34 @@ struct NgDirArgs {
     float damping, target_kl;
 };
 
-__global__ void __launch_bounds__(NG_BLOCK) ng_direction_kernel(const NgDirArgs a) {
+struct NgDirPopArgs {
+    NgDirArgs base;
+    size_t stride;
+    const float* damping;        // [P]
+    const float* target_kl;      // [P]
+};
+template <bool POP> struct NgDirKernelArgs { using type = NgDirArgs; };
+template <> struct NgDirKernelArgs<true> { using type = NgDirPopArgs; };
+__device__ __forceinline__ const NgDirArgs& ng_args_of(const NgDirArgs& a) { return a; }
+__device__ __forceinline__ NgDirArgs ng_args_of(const NgDirPopArgs& p) {
+    const uint32_t k = blockIdx.x;
+    NgDirArgs a = p.base;
+    a.z += k * p.stride;
+    a.x += k * p.stride;
+    a.b += k * p.stride;
+    a.step += k * p.stride;
+    a.theta += k * p.stride;
+    a.theta_old += k * p.stride;
+    a.st += (size_t)CF2_NG_STATE_DOUBLES * k;
+    if (a.gate) a.gate += 4u * (size_t)k;
+    a.damping = p.damping[k];
+    a.target_kl = p.target_kl[k];
+    return a;
+}
+
+template <bool POP = false>
+__global__ void __launch_bounds__(NG_BLOCK) ng_direction_kernel(const typename NgDirKernelArgs<POP>::type ka) {
+    const NgDirArgs a = ng_args_of(ka);
     __shared__ double wsum[NG_WAVES];
     const uint32_t tid = threadIdx.x;
     if (a.gate && a.gate[0] != 0u) return;
@@ -174,7 +238,32 @@ struct NgLsArgs {
     float decay, target_kl;
 };
 
-__global__ void __launch_bounds__(NG_BLOCK) ng_line_search_kernel(const NgLsArgs a) {
+struct NgLsPopArgs {
+    NgLsArgs base;               // eval: [P][8]; loss_before: member 0's word
+    size_t stride;
+    size_t loss_before_stride;   // doubles between the members' loss_before words
+    const float* target_kl;      // [P]
+};
+template <bool POP> struct NgLsKernelArgs { using type = NgLsArgs; };
+template <> struct NgLsKernelArgs<true> { using type = NgLsPopArgs; };
+__device__ __forceinline__ const NgLsArgs& ng_args_of(const NgLsArgs& a) { return a; }
+__device__ __forceinline__ NgLsArgs ng_args_of(const NgLsPopArgs& p) {
+    const uint32_t k = blockIdx.x;
+    NgLsArgs a = p.base;
+    a.theta += k * p.stride;
+    a.theta_old += k * p.stride;
+    a.step += k * p.stride;
+    a.eval += 8u * (size_t)k;
+    a.loss_before += k * p.loss_before_stride;
+    a.st += (size_t)CF2_NG_STATE_DOUBLES * k;
+    a.ctrl += 4u * (size_t)k;
+    a.target_kl = p.target_kl[k];
+    return a;
+}
+
+template <bool POP = false>
+__global__ void __launch_bounds__(NG_BLOCK) ng_line_search_kernel(const typename NgLsKernelArgs<POP>::type ka) {
+    const NgLsArgs a = ng_args_of(ka);
     const uint32_t tid = threadIdx.x;
     const bool stopped = a.ctrl[0] != 0u;
     const double loss = a.eval[1], kl = a.eval[4], before = *a.loss_before;
@@ -240,7 +329,7 @@ extern "C" int cf2_ng_cg_init(const float* grad_dev, float* b_dev, float* x_dev,
     if (!ng_slice(begin, count, &status)) return status;
     const NgCgArgs a = {grad_dev + begin, b_dev + begin, x_dev + begin, r_dev + begin, p_dev + begin, ng_state_dev,
                         ctrl_dev, count, 0.0f};
-    hipLaunchKernelGGL(ng_cg_init_kernel, dim3(1), dim3(NG_BLOCK), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(ng_cg_init_kernel<false>, dim3(1), dim3(NG_BLOCK), 0, (hipStream_t)stream, a);
     return ng_launched();
 }
 
@@ -256,7 +345,7 @@ extern "C" int cf2_ng_cg_step(const float* z_dev, float* x_dev, float* r_dev, fl
     if (!ng_slice(begin, count, &status)) return status;
     const NgCgArgs a = {z_dev + begin, nullptr, x_dev + begin, r_dev + begin, p_dev + begin, ng_state_dev, ctrl_dev,
                         count, damping};
-    hipLaunchKernelGGL(ng_cg_step_kernel, dim3(1), dim3(NG_BLOCK), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(ng_cg_step_kernel<false>, dim3(1), dim3(NG_BLOCK), 0, (hipStream_t)stream, a);
     return ng_launched();
 }
 
@@ -277,7 +366,7 @@ extern "C" int cf2_ng_direction(const float* z_dev, const float* x_dev, const fl
     if (!ng_slice(begin, count, &status)) return status;
     const NgDirArgs a = {z_dev + begin, x_dev + begin, b_dev + begin, step_dev + begin, weights_dev + begin,
                          weights_old_dev + begin, ng_state_dev, ctrl_dev, count, damping, target_kl};
-    hipLaunchKernelGGL(ng_direction_kernel, dim3(1), dim3(NG_BLOCK), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(ng_direction_kernel<false>, dim3(1), dim3(NG_BLOCK), 0, (hipStream_t)stream, a);
     return ng_launched();
 }
 
@@ -299,6 +388,99 @@ extern "C" int cf2_ng_line_search(float* weights_dev, const float* weights_old_d
     if (!ng_slice(begin, count, &status)) return status;
     const NgLsArgs a = {weights_dev + begin, weights_old_dev + begin, step_dev + begin, eval_summary_dev, loss_before_dev,
                         ng_state_dev, ctrl_dev, count, trial, total, decay, target_kl};
-    hipLaunchKernelGGL(ng_line_search_kernel, dim3(1), dim3(NG_BLOCK), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(ng_line_search_kernel<false>, dim3(1), dim3(NG_BLOCK), 0, (hipStream_t)stream, a);
+    return ng_launched();
+}
+
+// ---- populations (include/cf2sim.h: "The four solver calls for a population")
+// a population whose grid the launch cannot take
+static bool ng_pop_overflows(uint32_t members) { return members >= (1u << 31); }
+
+extern "C" int cf2_ng_cg_init_pop(uint32_t members, const float* grad_dev, float* b_dev, float* x_dev, float* r_dev,
+                                  float* p_dev, size_t block_stride, uint32_t begin, uint32_t count,
+                                  double* ng_state_dev, const uint32_t* ctrl_dev, void* stream) {
+    if (count == 0 || members == 0) return CF2_OK;
+    if (!grad_dev || !b_dev || !x_dev || !r_dev || !p_dev || !ng_state_dev) return CF2_ERR_INVALID_ARG;
+    if (misaligned(grad_dev, 4) || misaligned(b_dev, 4) || misaligned(x_dev, 4) || misaligned(r_dev, 4) ||
+        misaligned(p_dev, 4) || misaligned(ng_state_dev, 8) || misaligned(ctrl_dev, 4))
+        return CF2_ERR_INVALID_ARG;
+    if (ng_pop_overflows(members)) return CF2_ERR_INVALID_ARG;
+    int status = CF2_OK;
+    if (!ng_slice(begin, count, &status)) return status;
+    NgCgPopArgs p = {};
+    p.base = {grad_dev + begin, b_dev + begin, x_dev + begin, r_dev + begin, p_dev + begin, ng_state_dev, ctrl_dev, count,
+              0.0f};
+    p.stride = block_stride;
+    hipLaunchKernelGGL(ng_cg_init_kernel<true>, dim3(members), dim3(NG_BLOCK), 0, (hipStream_t)stream, p);
+    return ng_launched();
+}
+
+extern "C" int cf2_ng_cg_step_pop(uint32_t members, const float* z_dev, float* x_dev, float* r_dev, float* p_dev,
+                                  size_t block_stride, uint32_t begin, uint32_t count, const float* damping_dev,
+                                  double* ng_state_dev, const uint32_t* ctrl_dev, void* stream) {
+    if (count == 0 || members == 0) return CF2_OK;
+    if (!z_dev || !x_dev || !r_dev || !p_dev || !damping_dev || !ng_state_dev) return CF2_ERR_INVALID_ARG;
+    if (misaligned(z_dev, 4) || misaligned(x_dev, 4) || misaligned(r_dev, 4) || misaligned(p_dev, 4) ||
+        misaligned(damping_dev, 4) || misaligned(ng_state_dev, 8) || misaligned(ctrl_dev, 4))
+        return CF2_ERR_INVALID_ARG;
+    if (ng_pop_overflows(members)) return CF2_ERR_INVALID_ARG;
+    int status = CF2_OK;
+    if (!ng_slice(begin, count, &status)) return status;
+    NgCgPopArgs p = {};
+    p.base = {z_dev + begin, nullptr, x_dev + begin, r_dev + begin, p_dev + begin, ng_state_dev, ctrl_dev, count, 0.0f};
+    p.stride = block_stride;
+    p.damping = damping_dev;
+    hipLaunchKernelGGL(ng_cg_step_kernel<true>, dim3(members), dim3(NG_BLOCK), 0, (hipStream_t)stream, p);
+    return ng_launched();
+}
+
+extern "C" int cf2_ng_direction_pop(uint32_t members, const float* z_dev, const float* x_dev, const float* b_dev,
+                                    float* step_dev, float* weights_dev, float* weights_old_dev, size_t block_stride,
+                                    uint32_t begin, uint32_t count, const float* damping_dev, const float* target_kl_dev,
+                                    double* ng_state_dev, const uint32_t* ctrl_dev, void* stream) {
+    if (count == 0 || members == 0) return CF2_OK;
+    if (!z_dev || !x_dev || !b_dev || !step_dev || !weights_dev || !weights_old_dev || !damping_dev || !target_kl_dev ||
+        !ng_state_dev)
+        return CF2_ERR_INVALID_ARG;
+    if (misaligned(z_dev, 4) || misaligned(x_dev, 4) || misaligned(b_dev, 4) || misaligned(step_dev, 4) ||
+        misaligned(weights_dev, 4) || misaligned(weights_old_dev, 4) || misaligned(damping_dev, 4) ||
+        misaligned(target_kl_dev, 4) || misaligned(ng_state_dev, 8) || misaligned(ctrl_dev, 4))
+        return CF2_ERR_INVALID_ARG;
+    if (ng_pop_overflows(members)) return CF2_ERR_INVALID_ARG;
+    int status = CF2_OK;
+    if (!ng_slice(begin, count, &status)) return status;
+    NgDirPopArgs p = {};
+    p.base = {z_dev + begin, x_dev + begin, b_dev + begin, step_dev + begin, weights_dev + begin, weights_old_dev + begin,
+              ng_state_dev, ctrl_dev, count, 0.0f, 0.0f};
+    p.stride = block_stride;
+    p.damping = damping_dev, p.target_kl = target_kl_dev;
+    hipLaunchKernelGGL(ng_direction_kernel<true>, dim3(members), dim3(NG_BLOCK), 0, (hipStream_t)stream, p);
+    return ng_launched();
+}
+
+extern "C" int cf2_ng_line_search_pop(uint32_t members, float* weights_dev, const float* weights_old_dev,
+                                      const float* step_dev, size_t block_stride, uint32_t begin, uint32_t count,
+                                      uint32_t trial, uint32_t total, float decay, const float* target_kl_dev,
+                                      const double* eval_summary_dev, const double* loss_before_dev,
+                                      size_t loss_before_stride, double* ng_state_dev, uint32_t* ctrl_dev, void* stream) {
+    if (count == 0 || members == 0) return CF2_OK;
+    if (!weights_dev || !weights_old_dev || !step_dev || !target_kl_dev || !eval_summary_dev || !loss_before_dev ||
+        !ng_state_dev || !ctrl_dev)
+        return CF2_ERR_INVALID_ARG;
+    if (misaligned(weights_dev, 4) || misaligned(weights_old_dev, 4) || misaligned(step_dev, 4) ||
+        misaligned(target_kl_dev, 4) || misaligned(eval_summary_dev, 8) || misaligned(loss_before_dev, 8) ||
+        misaligned(ng_state_dev, 8) || misaligned(ctrl_dev, 4))
+        return CF2_ERR_INVALID_ARG;
+    if (trial >= total || !(decay > 0.0f) || !(decay <= 1.0f)) return CF2_ERR_INVALID_ARG;
+    if (ng_pop_overflows(members)) return CF2_ERR_INVALID_ARG;
+    int status = CF2_OK;
+    if (!ng_slice(begin, count, &status)) return status;
+    NgLsPopArgs p = {};
+    p.base = {weights_dev + begin, weights_old_dev + begin, step_dev + begin, eval_summary_dev, loss_before_dev,
+              ng_state_dev, ctrl_dev, count, trial, total, decay, 0.0f};
+    p.stride = block_stride;
+    p.loss_before_stride = loss_before_stride;
+    p.target_kl = target_kl_dev;
+    hipLaunchKernelGGL(ng_line_search_kernel<true>, dim3(members), dim3(NG_BLOCK), 0, (hipStream_t)stream, p);
     return ng_launched();
 }

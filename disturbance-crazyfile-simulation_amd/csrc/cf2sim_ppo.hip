@@ -786,10 +786,46 @@ struct FisherArgs {
     const uint32_t* gate;        // as PpoArgs::gate
 };
 
-template <int D>
-__global__ void __launch_bounds__(PPO_BLOCK) ppo_fisher_kernel(const FisherArgs a) {
+// P members in one launch (cf2_ppo_fisher_vec_pop; ppo_fisher_kernel<D, true>), as PpoPopArgs: `base`
+// holds member 0's pointers, member k's lie k strides (in elements) further on; block b serves member
+// b / bpm as that member's block b % bpm through the one kernel body.  s_idx == 0: one index list
+// that every member reads.  The gate word of member k is gate[4 k].
+struct FisherPopArgs {
+    FisherArgs base;             // n, m shared; part_sum, part_grad: member 0's slice of the scratch
+    size_t s_w, s_v, s_obs, s_idx;
+    size_t s_scratch;            // bytes between the members' scratch slices
+    uint32_t bpm;
+};
+
+__device__ __forceinline__ FisherArgs fisher_member_args(const FisherPopArgs& p, const uint32_t k) {
+    FisherArgs a = p.base;
+    a.W += k * p.s_w;
+    a.V += k * p.s_v;
+    a.obs += k * p.s_obs;
+    if (a.idx) a.idx += k * p.s_idx;
+    a.part_sum = reinterpret_cast<double*>(reinterpret_cast<char*>(a.part_sum) + k * p.s_scratch);
+    a.part_grad = reinterpret_cast<float*>(reinterpret_cast<char*>(a.part_grad) + k * p.s_scratch);
+    if (a.gate) a.gate += 4u * (size_t)k;
+    return a;
+}
+
+// the kernel argument and block geometry of an instance, as PpoKernelArgs above (the reason is there)
+template <bool POP> struct FisherKernelArgs { using type = FisherArgs; };
+template <> struct FisherKernelArgs<true> { using type = FisherPopArgs; };
+__device__ __forceinline__ const FisherArgs& fisher_args_of(const FisherArgs& a) { return a; }
+__device__ __forceinline__ FisherArgs fisher_args_of(const FisherPopArgs& p) {
+    return fisher_member_args(p, blockIdx.x / p.bpm);
+}
+__device__ __forceinline__ uint32_t ppo_block_of(const FisherArgs&) { return blockIdx.x; }
+__device__ __forceinline__ uint32_t ppo_block_of(const FisherPopArgs& p) { return blockIdx.x % p.bpm; }
+__device__ __forceinline__ uint32_t ppo_nblocks_of(const FisherArgs&) { return gridDim.x; }
+__device__ __forceinline__ uint32_t ppo_nblocks_of(const FisherPopArgs& p) { return p.bpm; }
+
+template <int D, bool POP = false>
+__global__ void __launch_bounds__(PPO_BLOCK) ppo_fisher_kernel(const typename FisherKernelArgs<POP>::type ka) {
     using N = PpoNet<D, true>;
     using L = PolicyLayout<D>;
+    const FisherArgs& a = fisher_args_of(ka);
     constexpr int H = N::H, NO = N::NO, WS = PPO_WS, AS = PPO_AS, ZS = PPO_ZS;
     constexpr int TAN = N::LDS_FLOATS;             // the direction's copy: the map of the weights, shifted
     constexpr int TAN_FLOATS = N::S_MEAN;          // W1 W2 W3 b1 b2 b3
@@ -879,7 +915,7 @@ __global__ void __launch_bounds__(PPO_BLOCK) ppo_fisher_kernel(const FisherArgs 
     for (int o = 0; o < NO; ++o) b3acc[o] = 0.0f;
     double S = 0.0;
 
-    const uint32_t ntiles = (a.m + 15u) / 16u, nwaves = gridDim.x * PPO_WAVES;
+    const uint32_t ntiles = (a.m + 15u) / 16u, nwaves = ppo_nblocks_of(ka) * PPO_WAVES;
     // the row of position 16 tile + c; a position past m reads row m - 1 and contributes nothing
     auto row_of = [&](uint32_t tile) {
         const uint32_t jc = __builtin_elementwise_min(tile * 16u + (uint32_t)c, a.m - 1u);
@@ -895,7 +931,7 @@ __global__ void __launch_bounds__(PPO_BLOCK) ppo_fisher_kernel(const FisherArgs 
             xr[it] = a.obs[(size_t)__shfl(row, r) * D + k];
         }
     };
-    uint32_t tile = blockIdx.x * PPO_WAVES + wave;
+    uint32_t tile = ppo_block_of(ka) * PPO_WAVES + wave;
     uint32_t row = row_of(tile < ntiles ? tile : ntiles - 1u);
     load_obs(row);
     for (; tile < ntiles; tile += nwaves) {
@@ -1082,7 +1118,7 @@ __global__ void __launch_bounds__(PPO_BLOCK) ppo_fisher_kernel(const FisherArgs 
         double v = 0.0;
         if (tid == 1)
             for (int w = 0; w < PPO_WAVES; ++w) v += sred[w];
-        a.part_sum[(size_t)blockIdx.x * PPO_SUM + tid] = v;
+        a.part_sum[(size_t)ppo_block_of(ka) * PPO_SUM + tid] = v;
     }
 
     // ---- the block's product: the waves add into LDS in wave order (wave 0 stores)
@@ -1141,7 +1177,7 @@ __global__ void __launch_bounds__(PPO_BLOCK) ppo_fisher_kernel(const FisherArgs 
         }
         __syncthreads();
     }
-    float* dst = a.part_grad + (size_t)blockIdx.x * N::NPAR;
+    float* dst = a.part_grad + (size_t)ppo_block_of(ka) * N::NPAR;
     for (int p = tid; p < N::NPAR; p += PPO_BLOCK) dst[p] = red[p];
 }
 
@@ -1156,6 +1192,27 @@ static int fisher_launch(FisherArgs a, float* out, double* summary, void* scratc
     if (e != hipSuccess) return hip_fail(e);
     hipLaunchKernelGGL(ppo_merge_kernel, dim3((N::NPAR + 255u) / 256u), dim3(256), 0, s, a.part_grad, a.part_sum, blocks,
                        (uint32_t)N::NPAR, a.m, out + N::BASE, summary, a.gate);
+    e = hipGetLastError();
+    return e == hipSuccess ? CF2_OK : hip_fail(e);
+}
+
+// the two launches of cf2_ppo_fisher_vec_pop; p.base and the strides are filled in by the caller
+template <int D>
+static int fisher_pop_launch(FisherPopArgs p, uint32_t members, float* out, size_t out_stride, double* summary,
+                             void* scratch, hipStream_t s) {
+    using N = PpoNet<D, true>;
+    p.bpm = ppo_blocks(p.base.m);
+    p.s_scratch = ppo_pop_slice_bytes(p.base.m, D);
+    p.base.part_sum = static_cast<double*>(scratch);
+    p.base.part_grad = reinterpret_cast<float*>(p.base.part_sum + (size_t)PPO_MAX_BLOCKS * PPO_SUM);
+    const uint32_t grid = members * p.bpm;         // below 2^31: checked by the caller
+    hipLaunchKernelGGL((ppo_fisher_kernel<D, true>), dim3(grid), dim3(PPO_BLOCK), 0, s, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e);
+    const uint32_t mblocks = (N::NPAR + 255u) / 256u;
+    hipLaunchKernelGGL(ppo_merge_pop_kernel, dim3(members * mblocks), dim3(256), 0, s, p.base.part_grad, p.base.part_sum,
+                       p.s_scratch, mblocks, p.bpm, (uint32_t)N::NPAR, p.base.m, out + N::BASE, out_stride, summary,
+                       p.base.gate);
     e = hipGetLastError();
     return e == hipSuccess ? CF2_OK : hip_fail(e);
 }
@@ -1321,6 +1378,28 @@ extern "C" int cf2_ppo_fisher_vec(const float* weights_dev, uint32_t obs_dim, co
     const hipStream_t s = (hipStream_t)stream;
     return obs_dim == 34 ? fisher_launch<34>(a, out_dev, summary_dev, scratch_dev, s)
                          : fisher_launch<42>(a, out_dev, summary_dev, scratch_dev, s);
+}
+
+extern "C" int cf2_ppo_fisher_vec_pop(uint32_t members, const float* weights_dev, size_t weights_stride, uint32_t obs_dim,
+                                      const float* obs_dev, size_t obs_stride, uint32_t n, const uint32_t* idx_dev,
+                                      size_t idx_stride, uint32_t m, const float* vec_dev, size_t vec_stride,
+                                      float* out_dev, size_t out_stride, double* summary_dev, void* scratch_dev,
+                                      const uint32_t* ctrl_dev, void* stream) {
+    if (obs_dim != 34 && obs_dim != 42) return CF2_ERR_UNSUPPORTED;
+    if (m == 0 || members == 0) return CF2_OK;
+    if (!weights_dev || !obs_dev || !vec_dev || !out_dev || !summary_dev || !scratch_dev || n == 0 || (!idx_dev && m > n))
+        return CF2_ERR_INVALID_ARG;
+    if (misaligned(weights_dev, 4) || misaligned(obs_dev, 8) || misaligned(idx_dev, 4) || misaligned(vec_dev, 4) ||
+        misaligned(out_dev, 4) || misaligned(summary_dev, 8) || misaligned(scratch_dev, 8) || misaligned(ctrl_dev, 4))
+        return CF2_ERR_INVALID_ARG;
+    if (stride_misaligned(obs_stride, 4, 8)) return CF2_ERR_INVALID_ARG;
+    if (ppo_pop_grid_overflows(members, m, obs_dim)) return CF2_ERR_INVALID_ARG;
+    FisherPopArgs p = {};
+    p.base = {weights_dev, vec_dev, obs_dev, idx_dev, nullptr, nullptr, n, m, ctrl_dev};
+    p.s_w = weights_stride, p.s_v = vec_stride, p.s_obs = obs_stride, p.s_idx = idx_stride;
+    const hipStream_t s = (hipStream_t)stream;
+    return obs_dim == 34 ? fisher_pop_launch<34>(p, members, out_dev, out_stride, summary_dev, scratch_dev, s)
+                         : fisher_pop_launch<42>(p, members, out_dev, out_stride, summary_dev, scratch_dev, s);
 }
 
 // ---- rank partials (include/cf2sim.h: "Data-parallel updates")

@@ -640,6 +640,35 @@ int  cf2_ppo_fisher_vec(const float* weights_dev, uint32_t obs_dim, const float*
                         const uint32_t* idx_dev, uint32_t m, const float* vec_dev, float* out_dev,
                         double* summary_dev, void* scratch_dev, const uint32_t* ctrl_dev, void* stream);
 
+/* cf2_ppo_fisher_vec for a population of `members` independent learners: it replaces `members`
+ * cf2_ppo_fisher_vec calls (two launches each) by two launches in all, under the contract of the
+ * population gradient calls above.  For every k < members, member k's out words and summary are the
+ * bits cf2_ppo_fisher_vec writes when given weights_dev + k weights_stride, obs_dev + k obs_stride,
+ * idx_dev + k idx_stride, vec_dev + k vec_stride, out_dev + k out_stride, summary_dev + 8 k and
+ * ctrl_dev + 4 k.  Nothing else is written: not the words between the members' slices, not the words
+ * of out outside [P_W1, P_LOGSTD).  Member k runs the grid it has alone, b = min(ceil(ceil(m / 16) /
+ * 4), 512) blocks, as blocks [k b, (k + 1) b) of one grid of members * b (one kernel body serves both
+ * forms); the merge is the population gradient calls'.  No atomics; the same input gives the same bits.
+ *   idx_dev      read-only.  idx_stride == 0: one list of m indices that every member reads (the
+ *                updaters' every-fourth-row list).  cf2_ppo_policy_grad_pop and cf2_ppo_value_grad_pop
+ *                add k * idx_stride in the same way, so a zero stride means a shared list there too;
+ *                they are unchanged.  NULL: rows 0..m-1 of every member.
+ *   summary_dev  [members][8] doubles
+ *   ctrl_dev     [members][4] uint32 or NULL: ungated.  A member whose word [4 k] is non-zero is skipped
+ *                in both launches -- its out, summary and scratch slice stay as they are -- and no
+ *                other member reads that word.
+ *   scratch_dev  cf2_ppo_pop_scratch_bytes(members, m, obs_dim) bytes, 8-byte aligned, sliced as the
+ *                population gradient calls slice it.
+ * Errors, all returned before anything is launched: obs_dim not 34 or 42: CF2_ERR_UNSUPPORTED; m == 0
+ * or members == 0: CF2_OK, nothing launched or written; a NULL weights, obs, vec, out, summary or
+ * scratch pointer, a misaligned base (4 bytes; 8 for obs, summary and scratch), an odd obs_stride, n ==
+ * 0, idx_dev == NULL with m > n, a grid of 2^31 blocks or more: CF2_ERR_INVALID_ARG. */
+int  cf2_ppo_fisher_vec_pop(uint32_t members, const float* weights_dev, size_t weights_stride, uint32_t obs_dim,
+                            const float* obs_dev, size_t obs_stride, uint32_t n, const uint32_t* idx_dev,
+                            size_t idx_stride, uint32_t m, const float* vec_dev, size_t vec_stride, float* out_dev,
+                            size_t out_stride, double* summary_dev, void* scratch_dev, const uint32_t* ctrl_dev,
+                            void* stream);
+
 /* Data-parallel updates: the gradient, evaluation and Fisher-vector calls above in two levels, so that
  * the ranks of a node update from all rows.  Level one, per rank: cf2_ppo_policy_partial,
  * cf2_ppo_value_partial and cf2_ppo_fisher_partial run the first launch of cf2_ppo_policy_grad_gated,
@@ -773,6 +802,42 @@ int  cf2_ng_line_search(float* weights_dev, const float* weights_old_dev, const 
                         uint32_t count, uint32_t trial, uint32_t total, float decay, float target_kl,
                         const double* eval_summary_dev, const double* loss_before_dev, double* ng_state_dev,
                         uint32_t* ctrl_dev, void* stream);
+
+/* The four solver calls for a population of `members` independent learners: each replaces `members`
+ * launches of its stand-alone twin (cf2_ng_cg_init, cf2_ng_cg_step, cf2_ng_direction,
+ * cf2_ng_line_search) by one launch of one 1 024-thread workgroup per member.  For every k < members,
+ * member k's words are the bits the stand-alone call writes when given base + k * block_stride for
+ * every flat-block vector (grad, b, x, r, p, z, step, weights, weights_old: block_stride floats apart,
+ * as cf2_adam_step_pop takes its blocks), damping_dev[k], target_kl_dev[k], ng_state_dev + 16 k,
+ * eval_summary_dev + 8 k, loss_before_dev + k * loss_before_stride (doubles; e.g. word 1 of a
+ * [members][8] summary with stride 8) and ctrl_dev + 4 k.  begin, count, trial, total and decay are
+ * shared.  The arithmetic is the stand-alone kernels': fp64 dot products in a fixed order, every
+ * written word rounded once.  Member k's workgroup is the only writer of member k's state, stop flag
+ * and weights and reads no other member's; nothing outside [begin, begin + count) of a member's blocks
+ * and nothing between the blocks is written.  A member whose gate word ctrl_dev[4 k] is set (or whose
+ * CG_DONE is set, in cg_step) is skipped while the others go on in the same launch.  damping_dev and
+ * target_kl_dev are device arrays of `members` floats, every value finite and >= 0: the caller's
+ * duty, the call cannot read them.
+ * count == 0 or members == 0: CF2_OK, nothing launched; a NULL pointer (every pointer but the gate of
+ * cg_init, cg_step and direction is required; cf2_ng_line_search_pop needs ctrl_dev), a misaligned
+ * base (4 bytes; 8 for ng_state, eval_summary and loss_before), members >= 2^31, begin + count past 32
+ * bits, decay outside (0, 1], trial >= total: CF2_ERR_INVALID_ARG; count > 2^20: CF2_ERR_UNSUPPORTED.
+ * Every error returns before anything is launched. */
+int  cf2_ng_cg_init_pop(uint32_t members, const float* grad_dev, float* b_dev, float* x_dev, float* r_dev, float* p_dev,
+                        size_t block_stride, uint32_t begin, uint32_t count, double* ng_state_dev,
+                        const uint32_t* ctrl_dev, void* stream);
+int  cf2_ng_cg_step_pop(uint32_t members, const float* z_dev, float* x_dev, float* r_dev, float* p_dev,
+                        size_t block_stride, uint32_t begin, uint32_t count, const float* damping_dev,
+                        double* ng_state_dev, const uint32_t* ctrl_dev, void* stream);
+int  cf2_ng_direction_pop(uint32_t members, const float* z_dev, const float* x_dev, const float* b_dev, float* step_dev,
+                          float* weights_dev, float* weights_old_dev, size_t block_stride, uint32_t begin, uint32_t count,
+                          const float* damping_dev, const float* target_kl_dev, double* ng_state_dev,
+                          const uint32_t* ctrl_dev, void* stream);
+int  cf2_ng_line_search_pop(uint32_t members, float* weights_dev, const float* weights_old_dev, const float* step_dev,
+                            size_t block_stride, uint32_t begin, uint32_t count, uint32_t trial, uint32_t total,
+                            float decay, const float* target_kl_dev, const double* eval_summary_dev,
+                            const double* loss_before_dev, size_t loss_before_stride, double* ng_state_dev,
+                            uint32_t* ctrl_dev, void* stream);
 
 /* Multi-GPU observation exchange as deltas (the north star's per-step RCCL
  * all-gather of the obs slab).  The reference has no counterpart: its MPI ranks exchange only
